@@ -39,6 +39,12 @@ cpu_baseline: the REFERENCE implementation itself (oracle/_ref, compiled from
 /root/reference sources: the AVX512 decoder if the host has it, else AVX2; the
 generic DFT for OFDM since FFTW is not in the image) on a bounded sample of the
 same workload, on the host cores of the same box, rank 0 only.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the result line
+(`ms_per_step`: wall milliseconds of one timed step).  Everything beyond that headline -- the CPU baseline, the
+probed / per-stage / per-kernel passes and rooflines, the latency, low-SNR and pinned sibling lines, the result
+self-checks -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (bench_outputs.py).
 """
 import argparse
 import gc
@@ -51,6 +57,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+from bench_outputs import dump_outputs  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md chip-level parameters (spec)
 
@@ -108,6 +116,12 @@ def parse():
     p.add_argument("--ues-per-cell", type=int, default=8, help="sch_slot: UEs sharing each cell's 273 PRBs")
     p.add_argument("--mixed", action="store_true",
                    help="slot_pipeline: ~20%% UCI-on-PUSCH, ~10%% HARQ retransmission, ~3%% DFT-s-OFDM PDUs")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: CPU baseline, probed / per-stage / per-kernel "
+                        "passes, rooflines, latency / low-SNR / pinned lines, result self-checks (each still has its "
+                        "own --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -153,7 +167,8 @@ def timed(args, dist, world, dev, stream, step, probes=None):
         sync()
         if probes and gpu:
             for p in [q for q in probes if isinstance(q, int)]:
-                profiling.arm(p, 64 * args.steps)
+                # a probe holds at most 2^16 launches (srs_amd_probe_arm); later launches of a long run go unrecorded
+                profiling.arm(p, min(64 * args.steps, 1 << 16))
         t0 = time.perf_counter()
         for s in range(args.steps):
             if gpu:
@@ -239,6 +254,7 @@ def run_ldpc(args, dist, world, rank, dev):
         dec.decode_batch(llrs, cfg, None, out=out, nof_iters=its, stream=stream)
 
     elapsed, kernel_ms = timed(args, dist, world, dev, stream, step)
+    dump_outputs(args, rank, {"messages": out, "iterations": its})
     total_cbs = args.batch * args.steps * world
     value = total_cbs / elapsed
     bytes_per_cb = N_LLRS + OUT_BYTES + 4  # LLRs in, packed message out, iteration count
@@ -246,7 +262,7 @@ def run_ldpc(args, dist, world, rank, dev):
     if rank != 0:
         return None
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = ldpc_cpu_baseline(args, llrs[:512].cpu().numpy())
     full_pmc = {}
     pmc_path = os.path.join(ROOT, "profiles", "r03c_ldpc_full_pmc.json")
@@ -355,31 +371,49 @@ def run_ofdm(args, dist, world, rank, dev):
 
     # per-kernel timing on the launch stream: modulator alone, demodulator alone
     elapsed, step_ms = timed(args, dist, world, dev, stream, step)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    ev[0].record(stream)
-    for _ in range(args.steps):
-        mod.modulate_batch(grid, 0, out=samples, stream=stream)
-    ev[1].record(stream)
-    for _ in range(args.steps):
-        dem.demodulate_batch(samples, 0, grid=back, stream=stream)
-    ev[2].record(stream)
-    torch.cuda.synchronize(dev)
-    mod_ms = ev[0].elapsed_time(ev[1]) / args.steps
-    dem_ms = ev[1].elapsed_time(ev[2]) / args.steps
+    dump_outputs(args, rank, {"samples": samples[:, :, :mod.get_slot_size(0)],
+                              "grid": back.view(torch.bfloat16).float()})
+    mod_ms = dem_ms = None
+    if args.full:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record(stream)
+        for _ in range(args.steps):
+            mod.modulate_batch(grid, 0, out=samples, stream=stream)
+        ev[1].record(stream)
+        for _ in range(args.steps):
+            dem.demodulate_batch(samples, 0, grid=back, stream=stream)
+        ev[2].record(stream)
+        torch.cuda.synchronize(dev)
+        mod_ms = ev[0].elapsed_time(ev[1]) / args.steps
+        dem_ms = ev[1].elapsed_time(ev[2]) / args.steps
 
     nsym = args.slots * OFDM_PORTS * 14
     # algorithmic HBM bytes: grid (cbf16, 4 B/RE) + samples (cf32, 8 B) once each way
     samp = sum(mod.get_slot_size(s % (1 << OFDM_MU)) for s in range(args.slots))
     mod_bytes = OFDM_PORTS * (args.slots * 14 * rg * 4 + samp * 8)
     dem_bytes = nsym * (OFDM_N * 8 + rg * 4)
-    mod_gbs = mod_bytes / (mod_ms * 1e-3) / 1e9
-    dem_gbs = dem_bytes / (dem_ms * 1e-3) / 1e9
     value = nsym * args.steps * world / elapsed
     if rank != 0:
         return None
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = ofdm_cpu_baseline(args, grid[:8, 0].cpu().numpy().view(np.uint16))
+    roofline = None
+    if args.full:
+        mod_gbs = mod_bytes / (mod_ms * 1e-3) / 1e9
+        dem_gbs = dem_bytes / (dem_ms * 1e-3) / 1e9
+        roofline = {
+            "bound": "hbm",
+            "achieved": (mod_bytes + dem_bytes) / ((mod_ms + dem_ms) * 1e-3) / 1e9,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": (mod_bytes + dem_bytes) / ((mod_ms + dem_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "traffic": load_traffic("r01_ofdm_traffic.json"),
+            "kernel": "ofdm_modulate_kernel<4096> + ofdm_demodulate_kernel<4096>",
+            "modulate": {"ms": mod_ms, "bytes": mod_bytes, "GB/s": mod_gbs},
+            "demodulate": {"ms": dem_ms, "bytes": dem_bytes, "GB/s": dem_gbs},
+            "step_event_ms": step_ms,
+        }
     return {
         "metric": "OFDM modulate+demodulate symbols/s (100 MHz numerology-1, 273 PRB, 4096-point DFT)",
         "value": value,
@@ -403,18 +437,7 @@ def run_ofdm(args, dist, world, rank, dev):
             "symbols_per_step_per_gpu": nsym,
             "parallelism": "slots sharded over ranks" if world > 1 else "single GPU",
         },
-        "roofline": {
-            "bound": "hbm",
-            "achieved": (mod_bytes + dem_bytes) / ((mod_ms + dem_ms) * 1e-3) / 1e9,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": (mod_bytes + dem_bytes) / ((mod_ms + dem_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "traffic": load_traffic("r01_ofdm_traffic.json"),
-            "kernel": "ofdm_modulate_kernel<4096> + ofdm_demodulate_kernel<4096>",
-            "modulate": {"ms": mod_ms, "bytes": mod_bytes, "GB/s": mod_gbs},
-            "demodulate": {"ms": dem_ms, "bytes": dem_bytes, "GB/s": dem_gbs},
-            "step_event_ms": step_ms,
-        },
+        "roofline": roofline,
         "cpu_baseline": cpu,
     }
 

@@ -16,7 +16,7 @@ Per slot (= one cell; `--slots-pipeline` cells per step and rank, all resident i
          tbs_lbrm_default, ZF, filter FD smoothing, average TD strategy (the reference app's default), CFO
          compensation).
 The PUSCH input is a UE transmission synthesised before the timed region through a
-fixed UL_LAYERS x 4 MIMO channel plus AWGN; every run checks the decoded TBs against
+fixed UL_LAYERS x 4 MIMO channel plus AWGN; a `--full` run checks the decoded TBs against
 what the UE sent. A step processes every slot of the batch through both chains;
 `value` counts the codeblocks encoded (PDSCH) plus decoded (PUSCH) per second.
 
@@ -30,6 +30,8 @@ import sys
 import time
 
 import numpy as np
+
+from bench_outputs import dump_outputs, records_to_columns
 
 NPRB, NSUBC, MU, NFFT = 273, 273 * 12, 1, 4096
 QM, RATE = 8, 948.0  # 256QAM, target code rate x 1024 (MCS 27 of the 256QAM table)
@@ -294,6 +296,17 @@ class Pipeline:
 
         return amd.pusch_processor.parse_results(self.res_ul.cpu().numpy())
 
+    def outputs(self):
+        """What a step hands to its caller (bench.py --dump-outputs): the PDSCH chain's baseband samples, the PUSCH
+        chain's transport blocks, per-PDU results (the fields of srs_amd_pusch_processor_result in order) and
+        per-port channel statistics."""
+        import srsran_project_amd as amd
+
+        return {"pdsch_samples": self.samp_dl[:, :, :self.ofdm_mod.get_slot_size(SLOT)],
+                "pusch_transport_blocks": self.tb_rx,
+                "pusch_results": records_to_columns(self.res_ul, amd.pusch_processor.PuschProcessorResult),
+                "pusch_port_stats": self.stats_ul}
+
     def check(self):
         """Fraction of PUSCH transport blocks with TB CRC ok and bit-equal to what the UE sent, and the mean LDPC
         iterations per codeblock."""
@@ -414,6 +427,52 @@ def latency_ms(dev, cells, steps=10, warmup=3, graph=False, **shape):
     return float(np.median(ts))
 
 
+def headline(args, pl, world, elapsed, ingest_ms):
+    """The result line of a plain run: the timed steps' throughput and what ran."""
+    S, L = pl.S, pl.ul_layers
+    cbs_dl, cbs_ul = pl.plan_dl.nof_segments, pl.plan_ul.nof_segments
+    cbs = (cbs_dl + cbs_ul) * S * args.steps * world
+    bits = (pl.tbs_dl + pl.tbs_ul) * S * args.steps * world
+    return {
+        "metric": "PDSCH+PUSCH codeblocks/s @ 100 MHz 273-PRB %dx%d MIMO (PDSCH %d layers, PUSCH %d layers x %d rx)"
+                  % (pl.dl_ports, pl.ul_ports, pl.dl_layers, L, pl.ul_ports),
+        "value": cbs / elapsed,
+        "unit": "codeblocks/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8+fp32",
+        "data": "synthetic (random transport blocks; PUSCH from a UE transmission through a %dx4 channel + AWGN "
+                "%.0f dB)" % (L, pl.snr_db),
+        "config": {
+            "workload": "BASELINE metric (PDSCH+PUSCH codeblocks/s @ 100 MHz 273-PRB %dx%d MIMO): full PDSCH+PUSCH "
+                        "slot pipeline, 100 MHz numerology-1 273 PRB, 256QAM R=948/1024" % (pl.dl_ports, pl.ul_ports)
+                        if (pl.dl_ports, pl.ul_ports) == (4, 4) else
+                        "configs[3] (%dx%d MIMO): full PDSCH+PUSCH slot pipeline, 100 MHz numerology-1 273 PRB, "
+                        "256QAM R=948/1024" % (pl.dl_ports, pl.ul_ports),
+            "cells_per_step_per_gpu": S,
+            "pdsch": {"layers": pl.dl_layers, "ports": pl.dl_ports, "tbs": pl.tbs_dl, "codeblocks": cbs_dl},
+            "pusch": {"layers": L, "rx_ports": pl.ul_ports, "tbs": pl.tbs_ul, "codeblocks": cbs_ul,
+                      "equalizer": pl.ul_equalizer,
+                      "equalizer_parity": "pinned (reference ZF)" if (L <= 2 and pl.ul_equalizer == "zf") or L == 1
+                      else "unpinned: the open reference asserts for this topology; fp64 solve within stated "
+                           "tolerance (tests/test_equalizer_mimo_gpu.py)",
+                      "ldpc_max_iterations": pl.iters, "early_stop": True,
+                      "chest_td": {0: "interpolate", 1: "average"}[pl.ul_td]},
+            "parallelism": ("cells sharded over ranks" + (", slot ingest scatter/gather over RCCL"
+                                                           if ingest_ms is not None else "")) if world > 1
+            else "single GPU",
+        },
+        "throughput_gbps": bits / elapsed / 1e9,
+        "hip_graph": bool(getattr(args, "graph", False)),
+        "ingest_ms_per_step": ingest_ms,
+    }
+
+
 def run_pipeline(args, dist, world, rank, dev, timed, hbm_peak, traffic=None):
     import torch
 
@@ -441,6 +500,7 @@ def run_pipeline(args, dist, world, rank, dev, timed, hbm_peak, traffic=None):
             fan.gather(pl.res_ul, full_res)
 
         elapsed, step_ms = timed(args, dist, world, dev, stream, ingest_step)
+        dump_outputs(args, rank, pl.outputs)
         el_compute, _ = timed(args, dist, world, dev, stream, lambda: pl.step(stream))
         ingest_ms = (elapsed - el_compute) / args.steps * 1e3
     else:
@@ -450,23 +510,24 @@ def run_pipeline(args, dist, world, rank, dev, timed, hbm_peak, traffic=None):
             run = pl.graph(stream)
         run = run or (lambda: pl.step(stream))
         elapsed, step_ms = timed(args, dist, world, dev, stream, run)
-        # the same K steps again with the live kernel probes armed: each probed launch carries timestamped events in
-        # its dispatch packet, which costs the step ~4 % (measured, profiles/r05_probe_overhead.json), so the
-        # headline value comes from the unprobed pass above and the kernel times from this one
+        dump_outputs(args, rank, pl.outputs)
+        # --full: the same K steps again with the live kernel probes armed: each probed launch carries timestamped
+        # events in its dispatch packet, which costs the step ~4 % (measured, profiles/r05_probe_overhead.json), so
+        # the headline value comes from the unprobed pass above and the kernel times from this one
         probes = None
-        if dev.type == "cuda" and not getattr(args, "no_probe", False):
+        if args.full and dev.type == "cuda" and not getattr(args, "no_probe", False):
             from srsran_project_amd import profiling as prof
 
             probes = {prof.PROBE_LDPC_HR: None, prof.PROBE_EQUALIZER: None, prof.PROBE_OFDM_DEMOD: None,
                       prof.PROBE_OFDM_MOD: None}
             el_probed, _ = timed(args, dist, world, dev, stream, run, probes=probes)
             probes["probed_ms_per_step"] = el_probed / args.steps * 1e3
+    line = headline(args, pl, world, elapsed, ingest_ms)
+    if not args.full:
+        # a plain run ends here: nothing below belongs to the headline figure
+        return line if rank == 0 else None
     ok_frac, its_mean = pl.check()
     stages = pl.stage_ms(stream)
-    cbs_dl, cbs_ul = pl.plan_dl.nof_segments, pl.plan_ul.nof_segments
-    cbs = (cbs_dl + cbs_ul) * S * args.steps * world
-    bits = (pl.tbs_dl + pl.tbs_ul) * S * args.steps * world
-    value = cbs / elapsed
     # the dominant kernel as the timed steps launched it (fused rate dematching: it reads each codeblock's E received
     # LLRs of the codeword, writes its message and iteration count), timed live by the probe on its own stream
     dec_cbs = pl.plan_ul.nof_segments * S
@@ -528,48 +589,12 @@ def run_pipeline(args, dist, world, rank, dev, timed, hbm_peak, traffic=None):
     pinned = None
     if world == 1 and L > 2 and not getattr(args, "no_pinned", False):
         pinned = pinned_sibling_line(args, dev, timed, dist, cpu)
-    return {
-        "metric": "PDSCH+PUSCH codeblocks/s @ 100 MHz 273-PRB %dx%d MIMO (PDSCH %d layers, PUSCH %d layers x %d rx)"
-                  % (pl.dl_ports, pl.ul_ports, pl.dl_layers, L, pl.ul_ports),
-        "value": value,
-        "unit": "codeblocks/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int8+fp32",
-        "data": "synthetic (random transport blocks; PUSCH from a UE transmission through a %dx4 channel + AWGN "
-                "%.0f dB)" % (L, pl.snr_db),
-        "config": {
-            "workload": "BASELINE metric (PDSCH+PUSCH codeblocks/s @ 100 MHz 273-PRB %dx%d MIMO): full PDSCH+PUSCH "
-                        "slot pipeline, 100 MHz numerology-1 273 PRB, 256QAM R=948/1024" % (pl.dl_ports, pl.ul_ports)
-                        if (pl.dl_ports, pl.ul_ports) == (4, 4) else
-                        "configs[3] (%dx%d MIMO): full PDSCH+PUSCH slot pipeline, 100 MHz numerology-1 273 PRB, "
-                        "256QAM R=948/1024" % (pl.dl_ports, pl.ul_ports),
-            "cells_per_step_per_gpu": S,
-            "pdsch": {"layers": pl.dl_layers, "ports": pl.dl_ports, "tbs": pl.tbs_dl, "codeblocks": cbs_dl},
-            "pusch": {"layers": L, "rx_ports": pl.ul_ports, "tbs": pl.tbs_ul, "codeblocks": cbs_ul,
-                      "equalizer": pl.ul_equalizer,
-                      "equalizer_parity": "pinned (reference ZF)" if (L <= 2 and pl.ul_equalizer == "zf") or L == 1
-                      else "unpinned: the open reference asserts for this topology; fp64 solve within stated "
-                           "tolerance (tests/test_equalizer_mimo_gpu.py)",
-                      "ldpc_max_iterations": pl.iters, "early_stop": True,
-                      "chest_td": {0: "interpolate", 1: "average"}[pl.ul_td]},
-            "parallelism": ("cells sharded over ranks" + (", slot ingest scatter/gather over RCCL"
-                                                           if ingest_ms is not None else "")) if world > 1
-            else "single GPU",
-        },
-        "throughput_gbps": bits / elapsed / 1e9,
+    line.update({
         "pusch_tb_ok_fraction": ok_frac,
         "pusch_ldpc_iterations_mean": its_mean,
         "stage_ms": stages,
         "stage_gbs": gbs,
         "latency_ms": lat,
-        "hip_graph": bool(getattr(args, "graph", False)),
-        "ingest_ms_per_step": ingest_ms,
         "low_snr": low,
         "pinned_sibling": pinned,
         "kernel_ms_in_step": in_step,
@@ -605,7 +630,8 @@ def run_pipeline(args, dist, world, rank, dev, timed, hbm_peak, traffic=None):
                     "slower, profiles/r06_ldpc_hr_ab.json).",
         },
         "cpu_baseline": cpu,
-    }
+    })
+    return line
 
 
 def valu_bound(cbs, its_mean, kernel_ms):

@@ -13,6 +13,8 @@ import time
 
 import numpy as np
 
+from bench_outputs import dump_outputs, records_to_columns
+
 NPRB, PORTS, MU, SLOT = 273, 4, 1, 3
 
 
@@ -130,9 +132,15 @@ def run_pucch(args, dist, world, rank, dev, timed):
         c34()
 
     elapsed, event_ms = timed(args, dist, world, dev, stream, step)
-    # per-format device time of one step (events around each slot call, after a synchronise)
+    dump_outputs(args, rank, lambda: {"f0_results": records_to_columns(r0, pu.RESULT_DTYPE),
+                                      "f1_results": records_to_columns(r1, pu.RESULT_DTYPE),
+                                      "f2_results": records_to_columns(r2, pu.UCI_RESULT_DTYPE),
+                                      "f34_results": records_to_columns(r34, pu.UCI_RESULT_DTYPE),
+                                      "f2_payloads": p2, "f34_payloads": p34})
+    # --full: per-format device time of one step (events around each slot call, after a synchronise)
     fmt_ms = {}
-    for name, fn in (("f0", c0), ("f1", c1), ("f2", c2), ("f34", c34)):
+    formats = (("f0", c0), ("f1", c1), ("f2", c2), ("f34", c34)) if args.full else ()
+    for name, fn in formats:
         torch.cuda.synchronize(dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
@@ -157,7 +165,7 @@ def run_pucch(args, dist, world, rank, dev, timed):
         "per_format": fmt_ms,
         "roofline": None,
     }
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         g0 = grids[0].cpu().numpy().view(np.uint32)
         line["cpu_baseline"] = cpu_baseline(args, amd, g0)
     return line

@@ -9,7 +9,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HW_PATH = os.path.join(_HERE, "_ref", "libsrsran_ref_hw.so")
-HAL_PATH = os.path.join(_HERE, "..", "integration", "_build", "libsrsran_amd_hal.so")
+HAL_PATH = os.path.join(_HERE, "_ref", "libsrsran_amd_hal.so")
 _lib = None
 
 

@@ -18,7 +18,9 @@ ROOT = os.path.join(os.path.dirname(__file__), "..")
                                   ["--workload", "pucch", "--slots-pipeline", "2", "--cpu-seconds", "0.2"]],
                          ids=["sch_slot", "slot_pipeline", "slot_pipeline_mixed", "pucch"])
 def test_bench_workload_line(args):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + args,
+    # --full: the per-workload extras (self-checks, per-format / per-UE timings) run too, as they always did here
+    common = ["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    r = subprocess.run([sys.executable, "bench.py"] + common + args,
                        cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -139,12 +139,12 @@ def test_sch_plan_host_only():
 
 
 def test_integration_plugins_built_against_reference_headers():
-    """integration/_build/libsrsran_amd_hal.so -- the srsRAN plug-ins over the C-ABI (hal::hw_accelerator_pusch_dec
+    """oracle/_ref/libsrsran_amd_hal.so -- the srsRAN plug-ins over the C-ABI (hal::hw_accelerator_pusch_dec
     and its factory, the PDSCH encoder plug-in, the ldpc_decoder / dft_processor / channel_equalizer factories), compiled against the reference's own headers -- exists, links
     with no undefined symbols (-Wl,--no-undefined) and exports the factory entry points."""
     import subprocess
 
-    path = os.path.join(os.path.dirname(__file__), "..", "integration", "_build", "libsrsran_amd_hal.so")
+    path = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "libsrsran_amd_hal.so")
     if not os.path.exists(path):
         pytest.skip("integration plug-ins not built (the reference headers are needed)")
     out = subprocess.run(["nm", "-D", "-C", "--defined-only", path], capture_output=True, text=True, check=True).stdout
@@ -157,7 +157,7 @@ def test_integration_plugins_built_against_reference_headers():
 
 
 def test_channel_processor_plugins_take_only_reference_interface_symbols():
-    """integration/_build/libsrsran_amd_phy.so -- the pusch / pdsch / pdcch / ssb / pucch processor plug-ins -- exports its factory
+    """oracle/_ref/libsrsran_amd_phy.so -- the pusch / pdsch / pdcch / ssb / pucch processor plug-ins -- exports its factory
     entry points and leaves undefined only the vtables / typeinfo of the reference's factory interfaces (their key
     function, create(srslog::basic_logger&), lives in the srsRAN library the plug-in is linked into) and
     rb_allocation::get_crb_mask; with the
@@ -165,7 +165,7 @@ def test_channel_processor_plugins_take_only_reference_interface_symbols():
     import subprocess
 
     root = os.path.join(os.path.dirname(__file__), "..")
-    path = os.path.join(root, "integration", "_build", "libsrsran_amd_phy.so")
+    path = os.path.join(root, "oracle", "_ref", "libsrsran_amd_phy.so")
     ref = os.path.join(root, "oracle", "_ref", "libsrsran_ref.so")
     if not os.path.exists(path) or not os.path.exists(ref):
         pytest.skip("channel-processor plug-ins not built (the reference headers are needed)")

@@ -7,7 +7,7 @@ set -uo pipefail
 out=$1
 mkdir -p "$out"
 export TMPDIR=/tmp
-timeout -k 10 420 python3 bench.py > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; exit 3; }
+timeout -k 10 420 python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; exit 3; }
 QUICK=(python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-latency --no-pinned --low-snr-db -1)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- "${QUICK[@]}" \
   > "$out/trace.log" 2>&1 || { echo "trace failed"; exit 3; }

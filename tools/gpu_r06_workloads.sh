@@ -8,7 +8,7 @@ mkdir -p "$out"
 run() {
   local name=$1
   shift
-  timeout -k 10 300 python3 bench.py "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "$name failed"; exit 3; }
+  timeout -k 10 300 python3 bench.py --full "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "$name failed"; exit 3; }
   echo "$name $(grep -o '"value": [0-9.e+]*' "$out/$name.json" | head -1)"
 }
 run ldpc --workload ldpc
