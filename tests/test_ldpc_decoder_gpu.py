@@ -7,12 +7,18 @@ reference's tests/unittests/phy/upper/channel_coding/ldpc/ldpc_enc_dec_test.cpp
 (all base graphs / lifting-size families, shortened lengths 24Z..66Z in 3 steps,
 zero and almost-zero LLR codeblocks) plus CRC early stop, filler bits,
 force_decoding, ragged batches and large batches.
+
+The strong-input tests at the end feed saturated LLRs (tests/ldpc_cases.py: beyond the +-64 clamp of full nodes, up
+to +-127, with every partial tail node holding such a value) to every kernel class, as ragged, unaligned and
+byte-offset rows, with filler bits next to the CRC, and through the persistent loop; tests/test_ldpc_cases.py checks
+on the oracle alone that those inputs reach what they are meant to.
 """
 import numpy as np
 import pytest
 
 import oracle
-from tests.ldpc_cases import noisy_codeblocks
+from tests import ldpc_cases
+from tests.ldpc_cases import noisy_codeblocks, strong_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -289,3 +295,159 @@ def test_packed_kernel_repeating_lanes(amd, bg):
     for Z in (144, 160, 176, 208, 224, 240, 288, 320, 352):
         msgs, llrs = noisy_codeblocks(bg, Z, 48, seed=Z * 13 + bg)
         _check(amd, dec, "simd", llrs, bg, Z, iters=6)
+
+
+# ---- strong inputs: saturated LLRs on every kernel class, ragged / unaligned rows, fillers, persistent loop
+_ORACLE_ROWS = {}
+
+
+def _oracle_rows(case, arith, crc, iters, force=False):
+    """Oracle decode of every row of a strong case (iterations or None, bits, soft bits), computed once for the
+    three kernel choices of the fixture and never modified."""
+    key = (case, arith, crc, iters, force)
+    if key not in _ORACLE_ROWS:
+        _, llrs = strong_inputs(case)
+        _ORACLE_ROWS[key] = [oracle.ldpc_decode(llrs[i, :L], case.bg, case.Z, iters, arith, crc, case.filler,
+                                                ldpc_cases.crc_len(crc), force_decoding=force, want_soft=True)
+                             for i, L in enumerate(case.lens)]
+    return _ORACLE_ROWS[key]
+
+
+def _device_rows(case, layout):
+    """The rows of a case on the device as (tensor [n, L], llr_lens or None).
+    ragged: full-length rows and per-row lengths; contiguous: [n, L], so an L that is no multiple of 4 gives an
+    unaligned stride; padded: a [:, :L] view of rows with a stride that is a multiple of 4, the rest of the codeblock
+    behind every row; +1: the same from a flat buffer starting at byte 1."""
+    import torch
+
+    _, llrs = strong_inputs(case)
+    n, N = llrs.shape
+    lens = None
+    if layout.startswith("ragged"):
+        L = N
+        lens = torch.from_numpy(np.asarray(case.lens, np.int32)).cuda()
+    else:
+        L = case.lens[0]
+        assert all(x == L for x in case.lens)
+    if layout == "contiguous":
+        return torch.from_numpy(np.array(llrs[:, :L])).cuda(), lens
+    W = (N + 8) & ~3
+    off = 1 if layout.endswith("+1") else 0
+    flat = np.full(off + n * W, 99, np.int8)
+    flat[off:].reshape(n, W)[:, :N] = llrs
+    d = torch.from_numpy(flat).cuda()
+    rows = torch.as_strided(d, (n, L), (W, 1), off)
+    assert rows.data_ptr() % 4 == off and rows.stride(0) % 4 == 0
+    return rows, lens
+
+
+def _launch(amd, dec, case, rows, lens, iters, crc, soft_offset=0):
+    import torch
+
+    bg, Z = case.bg, case.Z
+    n, nz = rows.shape[0], oracle.BG_N_FULL[bg] * Z
+    cfg = amd.LdpcDecoderConfiguration(base_graph=bg, lifting_size=Z, nof_filler_bits=case.filler,
+                                       nof_crc_bits=ldpc_cases.crc_len(crc), max_iterations=iters)
+    soft = torch.zeros(soft_offset + n * nz, dtype=torch.int8, device="cuda")[soft_offset:].view(n, nz)
+    assert soft.data_ptr() % 4 == soft_offset
+    out = torch.zeros((n, (oracle.BG_K[bg] * Z + 7) // 8), dtype=torch.uint8, device="cuda")
+    out, it = dec.decode_batch(rows, cfg, crc, llr_lens=lens, out=out, soft_out=soft)
+    torch.cuda.synchronize()
+    return out.cpu().numpy(), it.cpu().numpy(), soft.cpu().numpy()
+
+
+def _assert_rows(case, got, refs, what):
+    out, it, soft = got
+    assert len(refs) == out.shape[0]
+    for i, (r, o, s) in enumerate(refs):
+        where = "%s bg%d Z%d cb%d" % (what, case.bg, case.Z, i)
+        assert (-1 if r is None else r) == it[i], (where, r, it[i])
+        np.testing.assert_array_equal(out[i], o, err_msg="bits " + where)
+        np.testing.assert_array_equal(soft[i], s, err_msg="soft " + where)
+
+
+def _check_case(amd, dec, arith, case, layout, iters=None, crc="case", force=False, soft_offset=0):
+    crc = case.crc if crc == "case" else crc
+    iters = case.iters if iters is None else iters
+    rows, lens = _device_rows(case, layout)
+    got = _launch(amd, dec, case, rows, lens, iters, crc, soft_offset)
+    _assert_rows(case, got, _oracle_rows(case, arith, crc, iters, force), layout)
+    return got
+
+
+@pytest.mark.parametrize("arith", ["simd", "generic"])
+@pytest.mark.parametrize("Z", ldpc_cases.PARITY_ZS)
+@pytest.mark.parametrize("bg", [1, 2])
+def test_strong_inputs_every_kernel(amd, bg, Z, arith):
+    """Saturated LLRs through the clamp of every soft-bit load: one row per lane (Z = 7, 26; BG1 Z = 384 at 66 Z
+    unless the fixture forces the full-length kernel), packed with 1, 2 and 3 waves, high-rate (BG1 Z = 384 at 24 Z)
+    and full-length, with the CRC early stop and without."""
+    dec = amd.LdpcDecoder(arith)
+    for case in ldpc_cases.parity_cases():
+        if (case.bg, case.Z) == (bg, Z):
+            _check_case(amd, dec, arith, case, "contiguous")
+            _check_case(amd, dec, arith, case, "contiguous", iters=5, crc=None)
+
+
+@pytest.mark.parametrize("bg,Z", ldpc_cases.RAGGED_BZ)
+def test_strong_inputs_ragged_and_unaligned(amd, bg, Z):
+    """llr_lens with partial tail nodes of 1, 2, 7, Z - 3 and Z - 1 LLRs, and uniform lengths with L mod 4 = 1, 2, 3
+    (L mod Z = 1 and Z - 1 among them) as contiguous rows (unaligned stride: byte loads), as views of aligned rows
+    (word loads and the partial last word; the full-length kernel's for BG1 Z = 384) and from a base pointer one byte
+    off.  Every partial tail node holds +-127 and +-120, which only full nodes clamp."""
+    dec = amd.LdpcDecoder("simd")
+    rag = ldpc_cases.ragged_case(bg, Z)
+    a = _check_case(amd, dec, "simd", rag, "ragged")
+    b = _check_case(amd, dec, "simd", rag, "ragged+1")
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
+    for case in ldpc_cases.unaligned_cases(bg, Z):
+        assert case.lens[0] % 4 != 0
+        for layout in ("contiguous", "padded", "padded+1"):
+            _check_case(amd, dec, "simd", case, layout)
+
+
+@pytest.mark.parametrize("bg,Z,L", ldpc_cases.SOFT_OUT_CASES)
+def test_strong_inputs_soft_out_one_byte_off(amd, bg, Z, L):
+    """A soft_out that is not 4-byte aligned keeps the launch on the one-row-per-lane kernel (byte stores); same
+    result as the aligned launch."""
+    dec = amd.LdpcDecoder("simd")
+    case = ldpc_cases.soft_out_case(bg, Z, L)
+    a = _check_case(amd, dec, "simd", case, "contiguous")
+    b = _check_case(amd, dec, "simd", case, "contiguous", soft_offset=1)
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
+
+
+@pytest.mark.parametrize("arith", ["simd", "generic"])
+@pytest.mark.parametrize("bg,Z,L,crc,F", ldpc_cases.FILLER_CASES)
+def test_strong_inputs_crc_with_fillers(amd, bg, Z, L, crc, F, arith):
+    """CRC early stop over K Z - F bits with the filler boundary inside a 4-bit word (F mod 4 = 1, 2, 3), CRC16, 24A
+    and 24B, one and several waves per codeblock, filler positions that hold zeros and ones; 1 iteration, and 20 with
+    rows that never pass, so that the double-buffered CRC accumulators of the multi-wave kernels alternate many
+    times."""
+    dec = amd.LdpcDecoder(arith)
+    case = ldpc_cases.filler_case(bg, Z, L, crc, F)
+    for iters in (8, 1, 20):
+        _, it, _ = _check_case(amd, dec, arith, case, "contiguous", iters=iters)
+        assert (it == -1).any()
+        assert iters == 1 or (it >= 2).any()
+    # ones in the filler positions of rows whose CRC passes: zero filler bits would leave the remainder alone
+    _, it, _ = _check_case(amd, dec, arith, ldpc_cases.filler_case(bg, Z, L, crc, F, random_fillers=True), "contiguous")
+    assert (it >= 1).any()
+
+
+@pytest.mark.parametrize("bg,Z", ldpc_cases.PERSISTENT_BZ)
+def test_strong_inputs_persistent_loop(amd, bg, Z):
+    """11 ragged rows over 3 workgroups: every workgroup decodes a short row straight after a long one (the LDS still
+    holds the long row past the short one's input), and a row with fewer than K LLRs, which force_decoding skips, in
+    between.  Each row equals the oracle, the launch the same launch with a workgroup per row."""
+    case = ldpc_cases.persistent_case(bg, Z)
+    dec = amd.LdpcDecoder("simd", force_decoding=True)
+    dec.set_max_slots(3)
+    a = _check_case(amd, dec, "simd", case, "ragged", force=True)
+    assert a[1][case.short[0]] == -1 and not a[0][case.short[0]].any()
+    wide = amd.LdpcDecoder("simd", force_decoding=True)
+    b = _check_case(amd, wide, "simd", case, "ragged", force=True)
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
