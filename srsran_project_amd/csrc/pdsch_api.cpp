@@ -2,10 +2,10 @@
 // pdsch_encoder_impl::encode (lib/phy/upper/channel_processors/pdsch/pdsch_encoder_impl.cpp:28-80)
 // for a batch of transport blocks (srs_amd_pdsch_encode_batch) or a slot of heterogeneous ones
 // (srs_amd_pdsch_encode_slot), both through the fused chain of pdsch_encoder.hip:
-//   1. TB CRC (CRC16 / CRC24A) partials           pdsch_tb_crc_kernel   } concurrently (two helper streams)
-//   2. segmentation, CB CRC24B, LDPC encoding,    pdsch_cb_kernel       } over every codeblock but the TBs' last
-//      rate matching + concatenation                                   }
-//   3. the TBs' last codeblocks (TB CRC attached) pdsch_cb_kernel
+//   1. segmentation, CB CRC24B, LDPC encoding,    pdsch_cb_kernel   over every codeblock but the TBs' last; each
+//      rate matching + concatenation                                also stores its partial of the TB CRC
+//   2. the TBs' last codeblocks (TB CRC = XOR of  pdsch_cb_kernel   after 1. in stream order
+//      the partials and of their own bits)
 // SRSRAN_AMD_PDSCH_FUSED=0 (read per call) selects the previous five-stage chain instead (TB CRC, segmentation
 // + CB CRC, srs_amd_ldpc_encode_batch, srs_amd_ldpc_rate_match_batch), kept for A/B timing and cross-checks.
 #include "srsran_amd/crc.h"
@@ -88,7 +88,7 @@ struct fused_rows {
   std::vector<uint32_t>     row_E, row_out, row_geo, row_tb;
   std::vector<rm_geometry>  geos;
   std::vector<enc_row_desc> enc;
-  uint32_t                  max_tb_bytes = 0;
+  uint32_t                  max_segments = 0;
 };
 
 struct fused_layout {
@@ -127,7 +127,7 @@ void fused_add_tb(fused_rows& f, const srs_amd_sch_plan* p, uint64_t tb_offset, 
     f.row_tb.push_back(t);
     f.enc.push_back(er);
   }
-  f.max_tb_bytes = std::max(f.max_tb_bytes, p->tbs / 8);
+  f.max_segments = std::max(f.max_segments, p->nof_segments);
 }
 
 // Encoder row descriptor of plan p: lifted graph and the circular-buffer window [0, k0 + E + F) the rate matcher
@@ -141,15 +141,15 @@ enc_row_desc fused_enc_row(const srs_amd_sch_plan* p, const rm_geometry& g)
   return er;
 }
 
-// Writes the descriptors to dd (device) from the pinned staging buffer when `upload`, then runs the two launches.
+// Writes the descriptors to dd (device) from the pinned staging buffer when `upload`, then runs the two launches on
+// stream (launch_pdsch_fused).
 int fused_launch_locked(srs_amd_pdsch_encoder* e,
                         const fused_rows&      f,
                         uint8_t*               dd,
                         bool                   upload,
                         const uint8_t*         d_tbs,
                         uint8_t*               d_cw,
-                        hipStream_t            stream,
-                        bool                   overlap)
+                        hipStream_t            stream)
 {
   static const auto row_starts = [] {
     std::vector<int32_t> rs(2 * 47, 0);
@@ -163,7 +163,7 @@ int fused_launch_locked(srs_amd_pdsch_encoder* e,
   const fused_layout L(f);
   const uint32_t     U  = static_cast<uint32_t>(f.tds.size());
   const uint32_t     R  = static_cast<uint32_t>(f.row_E.size());
-  const uint32_t     part_stride = std::max(1u, (f.max_tb_bytes + PE_TB_CHUNK - 1) / PE_TB_CHUNK);
+  const uint32_t     part_stride = std::max(2u, f.max_segments) - 1; // a partial per codeblock but the TB's last
   hipError_t         he          = e->tb_parts.ensure(sizeof(uint32_t) * U * part_stride);
   if (he != hipSuccess) {
     return hip_fail(he, "PDSCH encoder TB CRC partials");
@@ -205,7 +205,6 @@ int fused_launch_locked(srs_amd_pdsch_encoder* e,
   a.edges        = ldpc_encoder_edges(e->enc);
   a.tb_parts     = e->tb_parts.as<uint32_t>();
   a.part_stride  = part_stride;
-  a.max_tb_bytes = f.max_tb_bytes;
   a.crc16_table  = crc_device_table(e->crc16);
   a.crc24a_table = crc_device_table(e->crc24a);
   a.crc24b_table = crc_device_table(e->crc24b);
@@ -217,21 +216,7 @@ int fused_launch_locked(srs_amd_pdsch_encoder* e,
   a.nof_cbs      = R;
   std::copy(row_starts.begin(), row_starts.begin() + 47, a.row_start[0]);
   std::copy(row_starts.begin() + 47, row_starts.end(), a.row_start[1]);
-  if (overlap) {
-    // TB CRC partials || codeblocks without a TB CRC, then the TBs' last codeblocks
-    he = e->fan.begin(stream, 2);
-    if (he == hipSuccess) {
-      he = launch_pdsch_fused(a, e->fan.stream(stream, 0), e->fan.stream(stream, 1), stream, 0);
-    }
-    if (he == hipSuccess) {
-      he = e->fan.end(stream);
-    }
-    if (he == hipSuccess) {
-      he = launch_pdsch_fused(a, stream, stream, stream, 1);
-    }
-  } else {
-    he = launch_pdsch_fused(a, stream, stream, stream, 2);
-  }
+  he = launch_pdsch_fused(a, stream);
   if (he == hipSuccess) {
     he = scope.close();
   }
@@ -275,13 +260,8 @@ int encode_fused_batch_locked(srs_amd_pdsch_encoder* e,
     return hip_fail(he, "PDSCH encoder descriptors");
   }
   e->batch_key.clear();
-  // a uniform batch of segmented TBs: with SRSRAN_AMD_PDSCH_OVERLAP=1 the TB CRC runs on a helper stream beside the
-  // codeblocks that do not carry it.  Off by default: inside the pipeline (PDSCH and PUSCH chains concurrent) the
-  // extra fork / join measured 0.864-0.877 ms per step against 0.851-0.863 ms without (tools/gpu_r04_fan2.sh).
-  const char* ov         = std::getenv("SRSRAN_AMD_PDSCH_OVERLAP"); // read per call (tests run both forms)
-  const bool  overlap_on = ov != nullptr && ov[0] == '1';
-  int rc = fused_launch_locked(e, f, e->batch_desc.as<uint8_t>(), upload, d_tbs, d_cw, stream,
-                               overlap_on && f.row_E.size() >= 4 * f.tds.size());
+  // (SRSRAN_AMD_PDSCH_OVERLAP is accepted and selects nothing: both launches go to `stream`)
+  int rc = fused_launch_locked(e, f, e->batch_desc.as<uint8_t>(), upload, d_tbs, d_cw, stream);
   if (rc == SRS_AMD_OK) {
     e->batch_key = std::move(key);
   }
@@ -334,8 +314,7 @@ int encode_fused_slot_locked(srs_amd_pdsch_encoder*  e,
   if (he != hipSuccess) {
     return hip_fail(he, "PDSCH slot encoder descriptors");
   }
-  // heterogeneous slots (many single-codeblock TBs): one stream, TB CRC partials then every codeblock
-  return fused_launch_locked(e, f, e->slot_desc.as<uint8_t>(), true, d_tbs, d_cw, stream, false);
+  return fused_launch_locked(e, f, e->slot_desc.as<uint8_t>(), true, d_tbs, d_cw, stream);
 }
 
 int encode_locked(srs_amd_pdsch_encoder* e,

@@ -1,11 +1,13 @@
 // pdsch_encoder.hip -- the PDSCH encoder chain of pdsch_encoder_impl::encode
 // (lib/phy/upper/channel_processors/pdsch/pdsch_encoder_impl.cpp:28-80):
-//   pdsch_tb_crc_kernel  the TB CRC (CRC16 / CRC24A, crc_calculator_generic_impl.cpp) as partials of PE_TB_CHUNK
-//                        bytes: byte-table remainders per thread combined in a tree, one move to the TB end per
-//                        chunk (crc_device.h); no accumulator to reset, no atomics;
 //   pdsch_cb_kernel      one wave per codeblock, everything in LDS:
-//                          segmentation (ldpc_segmenter_tx_impl.cpp:137-207): the message straight from the TB, the
-//                            TB CRC (XOR of the partials) on the last segment;
+//                          segmentation (ldpc_segmenter_tx_impl.cpp:137-207): the message straight from the TB;
+//                          the TB CRC (CRC16 / CRC24A, crc_calculator_generic_impl.cpp), which is linear in the TB's
+//                            bits: a codeblock that is not its TB's last divides its segment by the CRC24A byte
+//                            table in the pass that computes its CRC24B and stores the remainder in
+//                            tb_parts[TB][segment] -- every slot written on every call, no accumulator to reset, no
+//                            atomics; the TB's last codeblock moves each partial to the TB end (crc_device.h), XORs
+//                            them with the remainder of its own data bits and attaches the checksum after them;
 //                          the CRC24B of segmented TBs (ldpc_segmenter_tx_impl.cpp:196), byte table in LDS;
 //                          LDPC encoding (ldpc_encoder_impl.cpp:44-80) by the bit-sliced core (ldpc_encode_device.h)
 //                            with the lifted graph staged in LDS, only the circular-buffer window the rate matcher
@@ -14,12 +16,15 @@
 //                            whole bytes stored, the bytes shared with the neighbouring segments written with AND / OR
 //                            atomics on the segment's own bits (the codeword's padding bits cleared by the TB's last
 //                            segment), so no zeroing pass is needed.
-// The TB CRC kernel runs concurrently with the codeblock kernel over every codeblock but the TBs' last ones, which a
-// second codeblock launch encodes once the partials are in (pdsch_api.cpp).  (Gathering the TB CRC inside one launch
-// through a last-arriving workgroup needs an agent-scope fence per codeblock, which on the multi-XCD MI355X writes
-// back / invalidates L2 and measured twice as slow.)
+// Two launches on the caller's stream (launch_pdsch_fused): every codeblock but the TBs' last ones (skipped when no TB
+// is segmented), then the TBs' last codeblocks, one per TB.  Stream order is the only synchronisation: no workgroup
+// waits for another inside a launch.  (Gathering the TB CRC inside one launch through a last-arriving workgroup needs
+// an agent-scope fence per codeblock, which on the multi-XCD MI355X writes back / invalidates L2 and measured twice
+// as slow.)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "crc_device.h"
@@ -77,7 +82,6 @@ struct pe_lds {
   // the message (MSB-first bytes), then the encoded circular-buffer window (+ the second byte of a two-byte read)
   __attribute__((aligned(16))) uint8_t s_cw[PE_CW_BYTES + 8];
   uint32_t partial[4]; // block reductions (NT > 64)
-  uint32_t bcast[2];   // arrival count, TB CRC (NT > 64)
 };
 
 // XOR of v over the NT threads of the block (to every thread).
@@ -155,11 +159,65 @@ __device__ __forceinline__ void pe_message(const pdsch_fused_args& a, const tb_d
   }
 }
 
-// CRC24B (C > 1), LDPC encoding and rate matching of codeblock row `cb` whose message is in s_cw.
+// This thread's contributions to two 24-bit CRCs of the n-bit message in s_cw (MSB-first bytes) from its bytes
+// [b0, b1): crc_chunk_contrib twice (polynomial, linear table, byte table in LDS per CRC), as two independent division
+// chains over one fetch of the bytes.
+__device__ __forceinline__ void pe_crc24_pair(const uint8_t* s_cw, uint32_t b0, uint32_t b1, uint32_t n,
+                                              uint32_t polyA, const uint32_t* tableA, const uint32_t* TA,
+                                              uint32_t polyB, const uint32_t* tableB, const uint32_t* TB,
+                                              uint32_t& outA, uint32_t& outB)
+{
+  outA = 0;
+  outB = 0;
+  if (b0 >= b1) {
+    return;
+  }
+  constexpr uint32_t highbit = 1u << 24, mask = highbit - 1u;
+  const uint32_t     full    = min(b1, n / 8); // whole bytes
+  uint32_t           rA = 0, rB = 0;
+  for (uint32_t b = b0; b < full; b += CRC_FETCH_BATCH) {
+    uint32_t v[CRC_FETCH_BATCH];
+#pragma unroll
+    for (uint32_t k = 0; k < CRC_FETCH_BATCH; ++k) {
+      v[k] = b + k < full ? s_cw[b + k] : 0u;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < CRC_FETCH_BATCH; ++k) {
+      if (b + k < full) {
+        rA = TA[rA >> 16] ^ ((rA << 8) & mask) ^ v[k];
+        rB = TB[rB >> 16] ^ ((rB << 8) & mask) ^ v[k];
+      }
+    }
+  }
+  for (uint32_t b = max(b0, full); b < b1; ++b) {
+    const uint32_t byte = s_cw[b];
+    const int      nb   = (b * 8 + 8 <= n) ? 8 : static_cast<int>(n - b * 8);
+    for (int i = 0; i < nb; ++i) {
+      const uint32_t bit = (byte >> (7 - i)) & 1u;
+      rA                 = (rA << 1) | bit;
+      rB                 = (rB << 1) | bit;
+      rA ^= (rA & highbit) ? polyA : 0u;
+      rB ^= (rB & highbit) ? polyB : 0u;
+    }
+  }
+  // both remainders to the message end (table[k] = x^(k + 24) mod g)
+  const uint32_t  e  = min(n, b1 * 8);
+  const uint32_t* ta = tableA + (n - e);
+  const uint32_t* tb = tableB + (n - e);
+#pragma unroll
+  for (uint32_t j = 0; j < 24; ++j) {
+    outA ^= ta[j] & (0u - ((rA >> j) & 1u));
+    outB ^= tb[j] & (0u - ((rB >> j) & 1u));
+  }
+}
 
+// CRC24B (C > 1), LDPC encoding and rate matching of codeblock row `cb` (segment r of TB t) whose message is in s_cw.
+// A segment that is not its TB's last also stores its contribution to the TB CRC in tb_parts[t][r].
+// staged_off / staged_ne: the lifted graph s.edges holds (a workgroup that goes on to a codeblock of the same graph and
+// window, as every codeblock of a uniform batch is, keeps it).
 template <int NT>
-__device__ __forceinline__ void pe_finish(const pdsch_fused_args& a, pe_lds& s, uint32_t cb, const tb_desc& d,
-                                          uint32_t j)
+__device__ __forceinline__ void pe_finish(const pdsch_fused_args& a, pe_lds& s, uint32_t cb, uint32_t t,
+                                          const tb_desc& d, uint32_t j, uint32_t& staged_off, uint32_t& staged_ne)
 {
   const rm_geometry  g   = a.geos[a.row_geo[cb]];
   const enc_row_desc er  = a.enc_rows[cb];
@@ -176,10 +234,24 @@ __device__ __forceinline__ void pe_finish(const pdsch_fused_args& a, pe_lds& s, 
     const uint32_t nb  = (cbi + 7) / 8;
     const uint32_t per = (nb + NT - 1) / NT;
     const uint32_t b0  = j * per;
-    const uint32_t crc = pe_xor<NT>(
-        crc_chunk_contrib(lds_chunk_fetch{s_cw, 0}, b0, min(nb, b0 + per), cbi, 24, a.crc24b_poly, a.crc24b_table,
-                          s.T24b),
-        s.partial);
+    const uint32_t r   = cb - d.row0;
+    uint32_t       crc;
+    if (r + 1 < d.nof_segments) {
+      // the same bits are TB bits [r cbi, (r + 1) cbi): their CRC24A remainder (times x^24); the TB's last codeblock
+      // moves it to the TB end
+      uint32_t tb_part;
+      pe_crc24_pair(s_cw, b0, min(nb, b0 + per), cbi, a.crc24b_poly, a.crc24b_table, s.T24b, a.crc24a_poly,
+                    a.crc24a_table, s.Ttb, crc, tb_part);
+      crc     = pe_xor<NT>(crc, s.partial);
+      tb_part = pe_xor<NT>(tb_part, s.partial);
+      if (j == 0) {
+        a.tb_parts[static_cast<size_t>(t) * a.part_stride + r] = tb_part;
+      }
+    } else {
+      crc = pe_xor<NT>(crc_chunk_contrib(lds_chunk_fetch{s_cw, 0}, b0, min(nb, b0 + per), cbi, 24, a.crc24b_poly,
+                                         a.crc24b_table, s.T24b),
+                       s.partial);
+    }
     if (j == 0) {
       attach_crc_bits(s_cw, cbi, 24, crc);
     }
@@ -207,8 +279,12 @@ __device__ __forceinline__ void pe_finish(const pdsch_fused_args& a, pe_lds& s, 
   }
   const uint32_t* ge = a.edges + er.edge_off;
   const uint32_t  ne = static_cast<uint32_t>(a.row_start[bg - 1][er.M_eff]);
-  for (uint32_t e = j; e < ne; e += NT) {
-    s.edges[e] = ge[e];
+  if (er.edge_off != staged_off || ne != staged_ne) {
+    for (uint32_t e = j; e < ne; e += NT) {
+      s.edges[e] = ge[e];
+    }
+    staged_off = er.edge_off;
+    staged_ne  = ne;
   }
   __syncthreads();
   // ---- parity of the encoded window (edge descriptors from LDS: every edge read is then an LDS latency)
@@ -287,68 +363,19 @@ __device__ __forceinline__ void pe_finish(const pdsch_fused_args& a, pe_lds& s, 
   __syncthreads(); // s_cw / lw are rewritten by the next codeblock
 }
 
-// TB CRC partials: workgroup (chunk, t) divides TB bytes [chunk * PE_TB_CHUNK, + PE_TB_CHUNK), PE_TB_PER contiguous
-// bytes per thread by the byte table, combines the threads' remainders pairwise in a tree (left x^(bits of right) +
-// right, the powers from the linear table's first entries, hot in L2) and stores the chunk's remainder moved to the
-// TB end in tb_parts[t][chunk]: one move per chunk instead of one per thread, no accumulator, no atomics.
-constexpr int      PE_CRC_THREADS = 256;
-constexpr uint32_t PE_TB_PER      = PE_TB_CHUNK / PE_CRC_THREADS;
-
-__global__ __launch_bounds__(PE_CRC_THREADS) void pdsch_tb_crc_kernel(pdsch_fused_args a)
-{
-  __shared__ uint32_t T[256];
-  __shared__ uint32_t R[PE_CRC_THREADS];
-  __shared__ __attribute__((aligned(16))) uint8_t s_chunk[PE_TB_CHUNK];
-  uint32_t       table_order = 0, table_poly = 0;
-  const uint32_t i           = threadIdx.x;
-  for (uint32_t t = blockIdx.y; t < a.nof_tbs; t += gridDim.y) {
-    const tb_desc  d      = a.tds[t];
-    const uint32_t nbytes = d.tbs_bits / 8;
-    const uint32_t c0     = blockIdx.x * PE_TB_CHUNK;
-    if (c0 >= nbytes) {
-      continue; // uniform over the workgroup
-    }
-    const uint32_t  L     = d.tb_crc_bits;
-    const uint32_t  poly  = L == 16 ? a.crc16_poly : a.crc24a_poly;
-    const uint32_t* table = L == 16 ? a.crc16_table : a.crc24a_table;
-    const uint32_t  n     = min(PE_TB_CHUNK, nbytes - c0);
-    __syncthreads(); // T, R and s_chunk of the previous TB are no longer read
-    if (table_order != L || table_poly != poly) {
-      crc_table8_init<PE_CRC_THREADS>(T, L, poly);
-      table_order = L;
-      table_poly  = poly;
-    }
-    crc_stage_bytes<PE_CRC_THREADS>(s_chunk, a.tbs + d.tb_offset, c0, n); // coalesced
-    __syncthreads();
-    const uint32_t b0 = min(n, i * PE_TB_PER), b1 = min(n, b0 + PE_TB_PER);
-    R[i]              = crc_chunk_rem(lds_chunk_fetch{s_chunk, 0}, b0, b1, L, T);
-    __syncthreads();
-    // tree: R[i] <- R[i] x^(8 bytes of the right half) + R[i + h] over the threads' contiguous byte ranges
-#pragma unroll
-    for (uint32_t h = 1; h < PE_CRC_THREADS; h <<= 1) {
-      if ((i & (2 * h - 1)) == 0) {
-        const uint32_t rb0 = min(n, (i + h) * PE_TB_PER), rb1 = min(n, (i + 2 * h) * PE_TB_PER);
-        R[i] = crc_mulmod(R[i], crc_xpow(8 * (rb1 - rb0), L, table), L, poly) ^ R[i + h];
-      }
-      __syncthreads();
-    }
-    if (i == 0) {
-      // the chunk's message remainder, times x^(L + TB bits after the chunk)
-      a.tb_parts[static_cast<size_t>(t) * a.part_stride + blockIdx.x] =
-          crc_move(R[0], L + (d.tbs_bits - 8 * (c0 + n)), L, table);
-    }
-  }
-}
-
 template <int NT>
 __global__ __launch_bounds__(NT) void pdsch_cb_kernel(pdsch_fused_args a)
 {
   __shared__ pe_lds s;
+  // byte tables, once per workgroup: CRC24B, and the TB CRC's (CRC24A; a CRC16 TB rebuilds it below)
   crc_table8_init<NT>(s.T24b, 24, a.crc24b_poly);
-  const uint32_t j = threadIdx.x;
+  crc_table8_init<NT>(s.Ttb, 24, a.crc24a_poly);
+  uint32_t       tb_table_order = 24;
+  uint32_t       staged_off = 0, staged_ne = 0; // s.edges: nothing staged
+  const uint32_t j              = threadIdx.x;
 
-  // last_only 1: the TBs' last codeblocks (a.last_rows, one per TB, after the TB CRC partials); 0: every other
-  // codeblock (those carry no TB CRC and run while the partials are computed); 2: every codeblock (after the partials)
+  // last_only 0: every codeblock but the TBs' last ones (each stores its TB CRC partial); 1: the TBs' last codeblocks
+  // (a.last_rows, one per TB), launched after the others in stream order, so the partials are in
   const uint32_t n = a.last_only == 1 ? a.nof_tbs : a.nof_cbs;
   for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
     const uint32_t cb   = a.last_only == 1 ? a.last_rows[k] : k;
@@ -357,7 +384,7 @@ __global__ __launch_bounds__(NT) void pdsch_cb_kernel(pdsch_fused_args a)
     const uint32_t r    = cb - d.row0;
     const uint32_t C    = d.nof_segments;
     const bool     last = r == C - 1;
-    if (a.last_only == 0 && last) {
+    if ((a.last_only == 0) == last) {
       continue; // uniform over the workgroup
     }
     const uint32_t L    = d.tb_crc_bits;
@@ -365,67 +392,103 @@ __global__ __launch_bounds__(NT) void pdsch_cb_kernel(pdsch_fused_args a)
     // as pdsch_encoder_hw_impl's single segment does)
     const uint32_t n_data = last ? d.cb_info_bits - L - d.zero_pad : d.cb_info_bits;
     const uint32_t kz     = (a.geos[a.row_geo[cb]].nof_sys / a.enc_rows[cb].Z + 2) * a.enc_rows[cb].Z;
-    // ---- 1. the segment's TB data bits; the last segment: the TB CRC (XOR of the partials) after them
+    // ---- 1. the segment's TB data bits; the last segment: the TB CRC after them, the XOR of the other segments'
+    // partials and of the contribution of its own data bits (they end where the TB ends)
     uint32_t tb_crc = 0;
     if (last) {
-      const uint32_t np = (d.tbs_bits / 8 + PE_TB_CHUNK - 1) / PE_TB_CHUNK;
-      for (uint32_t i = j; i < np; i += NT) {
-        tb_crc ^= a.tb_parts[static_cast<size_t>(t) * a.part_stride + i];
+      if (tb_table_order != L) {
+        // (s.Ttb is not read between the barrier that ends the previous codeblock and the one after pe_message)
+        crc_table8_init<NT>(s.Ttb, L, L == 16 ? a.crc16_poly : a.crc24a_poly);
+        tb_table_order = L;
       }
-      tb_crc = pe_xor<NT>(tb_crc, s.partial);
+      for (uint32_t i = j; i + 1 < C; i += NT) {
+        // segment i's remainder, times x^(TB bits after the segment) (C > 1: CRC24A)
+        tb_crc ^= crc_move(a.tb_parts[static_cast<size_t>(t) * a.part_stride + i],
+                           d.tbs_bits - (i + 1) * d.cb_info_bits, 24, a.crc24a_table);
+      }
     }
     pe_message<NT>(a, d, r, n_data, kz, s.s_cw, j);
     __syncthreads();
-    if (last && j == 0) {
-      attach_crc_bits(s.s_cw, n_data, L, tb_crc); // zero padding stays zero after it
+    if (last) {
+      const uint32_t nb  = (n_data + 7) / 8;
+      const uint32_t per = (nb + NT - 1) / NT;
+      const uint32_t b0  = j * per;
+      tb_crc ^= crc_chunk_contrib(lds_chunk_fetch{s.s_cw, 0}, b0, min(nb, b0 + per), n_data, L,
+                                  L == 16 ? a.crc16_poly : a.crc24a_poly, L == 16 ? a.crc16_table : a.crc24a_table,
+                                  s.Ttb);
+      tb_crc = pe_xor<NT>(tb_crc, s.partial);
+      if (j == 0) {
+        attach_crc_bits(s.s_cw, n_data, L, tb_crc); // zero padding stays zero after it
+      }
+      __syncthreads();
     }
-    __syncthreads();
-    // ---- 2. CB CRC, encoding, rate matching
-    pe_finish<NT>(a, s, cb, d, j);
+    // ---- 2. CB CRC (with the TB CRC partial of a segment that is not the last), encoding, rate matching
+    pe_finish<NT>(a, s, cb, t, d, j, staged_off, staged_ne);
   }
+}
+
+constexpr int PE_MAX_DEVICES = 64;
+
+// Workgroups of pdsch_cb_kernel<NT> that are resident on the current device at once (by its registers and LDS).
+template <int NT>
+uint32_t pe_resident_workgroups()
+{
+  static std::atomic<uint32_t> known[PE_MAX_DEVICES] = {}; // per device, asked once
+  int                          dev = 0, per_cu = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PE_MAX_DEVICES) {
+    (void)hipGetLastError();
+    return 65535u;
+  }
+  uint32_t n = known[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pdsch_cb_kernel<NT>, NT, 0) != hipSuccess ||
+        per_cu <= 0) {
+      (void)hipGetLastError();
+      return 65535u;
+    }
+    n = static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(cus);
+    known[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
 
 } // namespace
 
-hipError_t launch_pdsch_fused(const pdsch_fused_args& a, hipStream_t crc_stream, hipStream_t cb_stream, hipStream_t stream,
-                              int phase)
+hipError_t launch_pdsch_fused(const pdsch_fused_args& a, hipStream_t stream)
 {
   if (a.nof_cbs == 0) {
     return hipSuccess;
   }
-  // threads per codeblock: SRSRAN_AMD_PDSCH_WG (read per launch) 256, else one wave
-  const char* wg  = std::getenv("SRSRAN_AMD_PDSCH_WG");
-  const bool  big = wg != nullptr && wg[0] == '2';
-  auto cb_launch = [&](const pdsch_fused_args& x, uint32_t n, hipStream_t st) {
-    const dim3 grid(n < 65535u ? n : 65535u);
-    if (big) {
-      hipLaunchKernelGGL(pdsch_cb_kernel<256>, grid, dim3(256), 0, st, x);
+  // threads per codeblock: SRSRAN_AMD_PDSCH_WG (read per launch) 256, else one wave.  The TBs' last codeblocks are
+  // one workgroup per TB, so that launch lasts as long as its slowest codeblock: four waves each (a low-rate Z = 384
+  // codeblock takes 36 us so, 72 us with one wave), SRSRAN_AMD_PDSCH_TAIL_WG=64: one wave
+  const char* wg       = std::getenv("SRSRAN_AMD_PDSCH_WG");
+  const char* tail     = std::getenv("SRSRAN_AMD_PDSCH_TAIL_WG");
+  const bool  big      = wg != nullptr && wg[0] == '2';
+  const bool  big_tail = tail == nullptr || tail[0] == '2';
+  // workgroups of the first launch: as many as stay resident, each looping over its codeblocks with the byte tables
+  // built and the lifted graph staged once (SRSRAN_AMD_PDSCH_GRID: that many instead; 65535: one per codeblock)
+  const char*    gs  = std::getenv("SRSRAN_AMD_PDSCH_GRID");
+  const uint32_t cap = gs != nullptr && std::atoi(gs) > 0 ? static_cast<uint32_t>(std::atoi(gs))
+                       : big                              ? pe_resident_workgroups<256>()
+                                                          : pe_resident_workgroups<64>();
+  auto cb_launch = [&](uint32_t last_only, uint32_t n, bool wide) {
+    pdsch_fused_args x = a;
+    x.last_only        = last_only;
+    const dim3 grid(std::min(n, last_only == 0 ? std::min(cap, 65535u) : 65535u));
+    if (wide) {
+      hipLaunchKernelGGL(pdsch_cb_kernel<256>, grid, dim3(256), 0, stream, x);
     } else {
-      hipLaunchKernelGGL(pdsch_cb_kernel<64>, grid, dim3(64), 0, st, x);
+      hipLaunchKernelGGL(pdsch_cb_kernel<64>, grid, dim3(64), 0, stream, x);
     }
   };
-  if (phase == 2) {
-    // one stream: the TB CRC partials, then every codeblock
-    hipLaunchKernelGGL(pdsch_tb_crc_kernel,
-                       dim3((a.max_tb_bytes + PE_TB_CHUNK - 1) / PE_TB_CHUNK, a.nof_tbs < 65535u ? a.nof_tbs : 65535u),
-                       dim3(PE_CRC_THREADS), 0, stream, a);
-    pdsch_fused_args b = a;
-    b.last_only        = 2;
-    cb_launch(b, a.nof_cbs, stream);
-  } else if (phase == 0) {
-    // the TB CRC partials and the codeblocks without a TB CRC, concurrently
-    hipLaunchKernelGGL(pdsch_tb_crc_kernel,
-                       dim3((a.max_tb_bytes + PE_TB_CHUNK - 1) / PE_TB_CHUNK, a.nof_tbs < 65535u ? a.nof_tbs : 65535u),
-                       dim3(PE_CRC_THREADS), 0, crc_stream, a);
-    pdsch_fused_args b = a;
-    b.last_only        = 0;
-    cb_launch(b, a.nof_cbs, cb_stream);
-  } else {
-    // the TBs' last codeblocks, once the partials are in
-    pdsch_fused_args b = a;
-    b.last_only        = 1;
-    cb_launch(b, a.nof_tbs, stream);
+  if (a.nof_cbs > a.nof_tbs) {
+    // every codeblock but the TBs' last ones: each stores its TB CRC partial
+    cb_launch(0, a.nof_cbs, big);
   }
+  // the TBs' last codeblocks, after the partials in stream order
+  cb_launch(1, a.nof_tbs, big_tail);
   return hipGetLastError();
 }
 

@@ -76,8 +76,8 @@ struct tx_slot_args {
 };
 hipError_t launch_tx_slot_segment(const tx_slot_args& a, hipStream_t stream);
 
-// Fused PDSCH encoder (pdsch_encoder.hip): TB CRC partials, then one workgroup per codeblock that builds,
-// CRC-attaches, LDPC-encodes and rate-matches its codeblock in LDS.
+// Fused PDSCH encoder (pdsch_encoder.hip): one workgroup per codeblock that builds, CRC-attaches, LDPC-encodes and
+// rate-matches its codeblock in LDS; the TB CRC is gathered from per-codeblock partials by the TB's last codeblock.
 struct pdsch_fused_args {
   const uint8_t*                 tbs;      // TB bytes (tds[t].tb_offset)
   const tb_desc*                 tds;      // per TB
@@ -88,9 +88,10 @@ struct pdsch_fused_args {
   const struct rm_geometry*      geos;
   const struct enc_row_desc*     enc_rows; // per codeblock: lifted graph, encoded window
   const uint32_t*                edges;    // every lifted graph (enc_row_desc::edge_off)
-  uint32_t*                      tb_parts; // [nof_tbs][part_stride] TB CRC partials (pdsch_tb_crc_kernel)
-  uint32_t                       part_stride;
-  uint32_t                       max_tb_bytes;
+  // [nof_tbs][part_stride] TB CRC partials: slot [t][r] is written by segment r < C - 1 of TB t on every call (the
+  // CRC24A remainder of the segment's bits times x^24; the TB's last codeblock moves it to the TB end)
+  uint32_t*                      tb_parts;
+  uint32_t                       part_stride; // max(1, largest C - 1)
   const uint32_t*                crc16_table;
   const uint32_t*                crc24a_table;
   const uint32_t*                crc24b_table;
@@ -102,11 +103,9 @@ struct pdsch_fused_args {
   uint32_t                       last_only; // set by launch_pdsch_fused
   int32_t                        row_start[2][47]; // check-row edge offsets of BG1 / BG2
 };
-constexpr uint32_t PE_TB_CHUNK = 8192; // TB bytes per partial of the TB CRC
-// phase 0: TB CRC partials on crc_stream, every codeblock but the TBs' last ones on cb_stream; phase 1 (after both):
-// the TBs' last codeblocks on stream; phase 2: the TB CRC partials, then every codeblock, on stream.
-hipError_t launch_pdsch_fused(const pdsch_fused_args& a, hipStream_t crc_stream, hipStream_t cb_stream,
-                              hipStream_t stream, int phase);
+// Two launches on stream: every codeblock but the TBs' last ones, which store their TB CRC partials (skipped when no
+// TB is segmented), then the TBs' last codeblocks, which read them.
+hipError_t launch_pdsch_fused(const pdsch_fused_args& a, hipStream_t stream);
 
 // pusch_decoder_impl.cpp:309-500 after the decoder: per-CB CRC status (kept in the
 // soft buffer across HARQ transmissions), statistics, codeblock concatenation
