@@ -125,3 +125,16 @@ from . import ssb  # noqa: F401,E402
 from .ssb import SsbPatternCase, SsbPdu, SsbProcessor  # noqa: F401,E402
 from . import pucch  # noqa: F401,E402
 from .pucch import PucchF0Pdu, PucchF1Batch, PucchF2Pdu, PucchF34Pdu, PucchProcessor  # noqa: F401,E402
+from . import prach  # noqa: F401,E402
+from .prach import (  # noqa: F401,E402
+    PrachBatch,
+    PrachConfiguration,
+    PrachDetectionResult,
+    PrachDetector,
+    PrachFormat,
+    PrachGeometry,
+    PrachPreambleIndication,
+    PrachSubcarrierSpacing,
+    prach_geometry,
+    prach_physical_root,
+)
