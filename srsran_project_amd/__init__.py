@@ -138,3 +138,14 @@ from .prach import (  # noqa: F401,E402
     prach_geometry,
     prach_physical_root,
 )
+from . import srs  # noqa: F401,E402
+from .srs import (  # noqa: F401,E402
+    SrsBatch,
+    SrsConfiguration,
+    SrsEstimationResult,
+    SrsEstimator,
+    SrsInformation,
+    srs_bandwidth,
+    srs_information,
+    srs_validate,
+)
