@@ -466,20 +466,13 @@ __device__ __forceinline__ void run_layers(lds_i8*       soft,
 // Occupancy target: 4 waves per SIMD (<= 128 VGPRs).  A Z=384 workgroup is 6
 // waves; two of them fit a CU whatever SIMD the dispatcher starts them on only
 // if every SIMD can hold 4 (at 3 per SIMD the second workgroup is mostly refused).
-template <int BG, int ZC>
-constexpr int waves_per_simd()
-{
-  return 4;
-}
+constexpr int WAVES_PER_SIMD = 4;
 
 // Check rows per wavefront.  64 for every Z except the compile-time Z=384
 // kernel, which may spread its 384 rows over 8 waves of 48 (lanes 48-63 then
 // duplicate rows 32-47: identical values to identical addresses), so that two
 // workgroups put exactly 2 + 2 waves on every SIMD instead of 2/2/1/1 + 1/1/2/2.
-#ifndef Z384_CPW
-#define Z384_CPW 48
-#endif
-constexpr int Z384_CHECKS_PER_WAVE = Z384_CPW;
+constexpr int Z384_CHECKS_PER_WAVE = 48;
 template <int ZC>
 constexpr int checks_per_wave()
 {
@@ -492,7 +485,7 @@ constexpr int max_threads()
 }
 
 template <int BG, int ARITH, int ZC>
-__global__ void __launch_bounds__(max_threads<ZC>(), (waves_per_simd<BG, ZC>())) ldpc_decode_kernel(decode_args a, lifted_graph g)
+__global__ void __launch_bounds__(max_threads<ZC>(), WAVES_PER_SIMD) ldpc_decode_kernel(decode_args a, lifted_graph g)
 {
   constexpr int NW      = reg_words<BG>();
   constexpr int N_FULL  = bg_traits<BG>::N_FULL;
@@ -807,42 +800,26 @@ __host__ __device__ constexpr int hr_lds_bytes()
   return LDS_SOFT_OFFSET + (22 + MAXL) * HR_Z;
 }
 
-// LDS byte offset of the soft bit that row (t + KOFF + H) of edge EI reads, H = 0 or 192, t + KOFF < 192.
+// LDS byte offset of the soft bit that row (t + H) of edge EI reads, H = 0 or 192, t < 192.
 // One of the two rows of an edge never wraps: its address is t + literal.
-template <int EI, int H, int KOFF = 0>
+template <int EI, int H>
 __device__ __forceinline__ uint32_t hr_addr(uint32_t t)
 {
   constexpr uint32_t s    = (const_edge<1, HR_Z, EI>::shift + H) % HR_Z;
   constexpr uint32_t base = LDS_SOFT_OFFSET + const_edge<1, HR_Z, EI>::var * HR_Z;
   if constexpr (s <= HR_HALF) {
-    return t + (base + KOFF + s); // t + KOFF < 192: t + KOFF + s < 384
+    return t + (base + s); // t < 192: t + s < 384
   } else {
-    return __builtin_elementwise_min(t + (KOFF + s), t + (KOFF + s - HR_Z)) + base;
+    return __builtin_elementwise_min(t + s, t + (s - HR_Z)) + base;
   }
 }
 
-// Compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>).
-template <int N, typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>)
-{
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f)
-{
-  static_for_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
-
-// Check-to-variable messages of the first MAXL layers, register resident: one int16 pair per edge
-// (default), or (HR_PACK8) two edges per VGPR as int8 pairs, edge 2w in the high byte and edge 2w+1
-// in the low byte of each 16-bit half, unpacked with one or two packed shifts and repacked with one
-// v_perm_b32.  Measured (tools/ldpc_hr_probe.py, 4,544 codeblocks): the layers are VALU-bound, and
-// the 2.5 extra VALU per edge of the int8 form cost more (75.6 vs 70.2 us per iteration) than its
-// occupancy gain (98 vs 128 VGPRs) returns; the edge chunking (5, 10, 19) changes nothing.
-#ifndef HR_PACK8
-#define HR_PACK8 0
-#endif
-template <int NE, bool PACK8 = HR_PACK8>
+// Check-to-variable messages of the first MAXL layers, register resident: one int16 pair per edge.
+// Two edges per VGPR as int8 pairs were measured (tools/ldpc_hr_probe.py, 4,544 codeblocks): the
+// layers are VALU-bound, and the 2.5 extra VALU per edge of the int8 form cost more (75.6 vs 70.2 us
+// per iteration) than its occupancy gain (98 vs 128 VGPRs) returns; the edge chunking (5, 10, 19)
+// changes nothing.
+template <int NE>
 struct hr_msgs {
   pk16 m[NE];
   __device__ __forceinline__ void zero()
@@ -856,37 +833,6 @@ struct hr_msgs {
   __device__ __forceinline__ pk16 get() const { return m[E]; }
   template <int E>
   __device__ __forceinline__ void set(pk16 c) { m[E] = c; }
-};
-template <int NE>
-struct hr_msgs<NE, true> {
-  uint32_t w[(NE + 1) / 2];
-  __device__ __forceinline__ void zero()
-  {
-#pragma unroll
-    for (int e = 0; e < (NE + 1) / 2; ++e) {
-      w[e] = 0;
-    }
-  }
-  template <int E>
-  __device__ __forceinline__ pk16 get() const
-  {
-    const pk16 x = __builtin_bit_cast(pk16, w[E >> 1]);
-    if constexpr ((E & 1) == 0) {
-      return x >> 8;
-    } else {
-      return (x << 8) >> 8;
-    }
-  }
-  template <int E>
-  __device__ __forceinline__ void set(pk16 c)
-  {
-    const uint32_t cv = __builtin_bit_cast(uint32_t, c);
-    // v_perm_b32(src0 = c, src1 = w): selector bytes 0-3 pick w, 4-7 pick c
-    w[E >> 1] = __builtin_amdgcn_perm(cv, w[E >> 1], (E & 1) == 0 ? 0x06020400u : 0x03060104u);
-    // pin the repacked word here: left alone the compiler sinks the v_perm_b32 to the end of the
-    // iteration and keeps every new message unpacked (and spilled) until then
-    asm volatile("" : "+v"(w[E >> 1]));
-  }
 };
 
 template <int ARITH>
@@ -945,285 +891,83 @@ __device__ __forceinline__ pk16 pk_key(pk16 a)
 }
 
 // Edges per scheduling group in the two passes of a layer (bounds the gathered values in flight).
-#ifndef HR_CHUNK1
-#define HR_CHUNK1 5
-#endif
-#ifndef HR_CHUNK2
-#define HR_CHUNK2 5
-#endif
-#ifndef HR_PIN_X
-#define HR_PIN_X 0
-#endif
-// argmin as the low bits of min(|v2c| << 5 | e) (as the full-length kernel below): pass 2 tests e == idx with two
-// instructions instead of recomputing |v2c| - min1 (four)
-#ifndef HR_KEYS
-#define HR_KEYS 0
-#endif
+constexpr int HR_CHUNK1 = 5;
+constexpr int HR_CHUNK2 = 5;
 
-// One layer (base-graph row L, global edges E0 .. E0 + DEG - 1) for the NP row pairs of lane t:
-// rows t + k T and t + k T + 192, T = 192 / NP, k < NP (message of edge e, pair k: index e NP + k).
+// One layer (base-graph row L, global edges E0 .. E0 + DEG - 1) for the row pair of lane t: rows t and t + 192.
 //
 // Instruction scheduling (gfx950): a packed-math (VOP3P) result read by the very next VOP3P instruction costs a
 // hazard s_nop, and those nops took ~35 % of the issue slots of a dependent v_pk_* chain at 4 waves per SIMD
 // (scratch microbenchmark; the kernel is VALU-issue bound at ~4.3 cycles per v_pk_* wave instruction).  So the
 // check-node reduction runs as two independent chains (even / odd edges, merged at the end of pass 1), and pass 2
 // leaves the scheduler free to interleave consecutive edges (no ordering fence between them).
-template <int L, int ARITH, int NP, typename MSGS, int... E>
+template <int L, int ARITH, typename MSGS, int... E>
 __device__ __forceinline__ void hr_layer(lds_i8* lds, MSGS& c2v, uint32_t t, std::integer_sequence<int, E...>)
 {
   constexpr int E0  = row_start<1>(L);
   constexpr int DEG = sizeof...(E);
-  constexpr int T   = HR_HALF / NP;
-  pk16          v[DEG][NP];
-  pk16          min1[2][NP], min2[2][NP], sgn[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    // HR_KEYS: minima of the keys |v2c| << 5 | e (the initial key stands for LLR_MAX with no edge index)
-    min1[0][k] = min1[1][k] = pk_splat(HR_KEYS ? LLR_MAX * 32 + 31 : LLR_MAX);
-    min2[0][k] = min2[1][k] = pk_splat(HR_KEYS ? LLR_MAX * 32 + 31 : LLR_MAX);
-    sgn[k]                  = pk_splat(0);
-  }
+  pk16          v[DEG];
+  pk16          min1[2], min2[2];
+  min1[0] = min1[1] = pk_splat(LLR_MAX);
+  min2[0] = min2[1] = pk_splat(LLR_MAX);
   // pass 1 (ldpc_decoder_impl.cpp:235 / :290): v2c and the check-node statistics
   (
       [&] {
         if constexpr (E % HR_CHUNK1 == 0 && E > 0) {
           __builtin_amdgcn_sched_barrier(0);
         }
-        static_for<NP>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          constexpr int h = E & 1; // reduction chain
-          const pk16    s = pk16{static_cast<short>(lds[hr_addr<E0 + E, 0, k * T>(t)]),
-                              static_cast<short>(lds[hr_addr<E0 + E, HR_HALF, k * T>(t)])};
-          const pk16 sat = pk_clamp(s, LLR_MAX);
-          // infinite soft bits (+-SOFT_INF) push |v2c| beyond 220 (see edge_pass1)
-          const pk16 x = (s - sat) * pk_splat(INF_BOOST) + pk_clamp(s - c2v.template get<(E0 + E) * NP + k>(), LLR_MAX);
-#if HR_KEYS
-          const pk16 ax = pk_key<E>(__builtin_elementwise_abs(x));
-#else
-          const pk16 ax = __builtin_elementwise_abs(x);
-#endif
-          min2[h][k]    = pk_max(min1[h][k], pk_min(ax, min2[h][k])); // median(min1, |v|, min2)
-          min1[h][k]    = pk_min(min1[h][k], ax);
-          sgn[k] ^= x;
-          v[E][k] = x;
-        });
+        constexpr int h = E & 1; // reduction chain
+        const pk16    s = pk16{static_cast<short>(lds[hr_addr<E0 + E, 0>(t)]),
+                            static_cast<short>(lds[hr_addr<E0 + E, HR_HALF>(t)])};
+        const pk16 sat = pk_clamp(s, LLR_MAX);
+        // infinite soft bits (+-SOFT_INF) push |v2c| beyond 220 (see edge_pass1)
+        const pk16 x  = (s - sat) * pk_splat(INF_BOOST) + pk_clamp(s - c2v.template get<E0 + E>(), LLR_MAX);
+        const pk16 ax = __builtin_elementwise_abs(x);
+        min2[h]       = pk_max(min1[h], pk_min(ax, min2[h])); // median(min1, |v|, min2)
+        min1[h]       = pk_min(min1[h], ax);
+        v[E]          = x;
       }(),
       ...);
   __builtin_amdgcn_sched_barrier(0);
-  pk16 m1[NP], s1[NP], s2[NP], d12[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    // merge the two chains: min1 = min(a1, b1), min2 = min(max(a1, b1), min(a2, b2))
-    m1[k]  = pk_min(min1[0][k], min1[1][k]);
-    const pk16 mn2 = pk_min(pk_max(min1[0][k], min1[1][k]), pk_min(min2[0][k], min2[1][k]));
-#if HR_KEYS
-    s1[k]  = pk_scale16<ARITH>(m1[k] >> 5);
-    s2[k]  = pk_scale16<ARITH>(mn2 >> 5);
-    m1[k]  = as_pk(as_u32(m1[k]) & 0x001f001fu); // index of the first minimum
-#else
-    s1[k]  = pk_scale<ARITH>(m1[k]);
-    s2[k]  = pk_scale<ARITH>(mn2);
-#endif
-    d12[k] = s1[k] - s2[k];
-  }
+  // merge the two chains: min1 = min(a1, b1), min2 = min(max(a1, b1), min(a2, b2))
+  const pk16 m1  = pk_min(min1[0], min1[1]);
+  const pk16 mn2 = pk_min(pk_max(min1[0], min1[1]), pk_min(min2[0], min2[1]));
+  const pk16 s1  = pk_scale<ARITH>(m1);
+  const pk16 s2  = pk_scale<ARITH>(mn2);
+  const pk16 d12 = s1 - s2;
+  // sign product of the row, taken here and not edge by edge in pass 1: the xor chain stays out of the
+  // scheduling groups of the gathers
+  const pk16 sgn = (pk_splat(0) ^ ... ^ v[E]);
   // pass 2 (ldpc_decoder_impl.cpp:310, :270): new message and promotion sum
   (
       [&] {
         if constexpr (E % HR_CHUNK2 == 0 && E > 0) {
           __builtin_amdgcn_sched_barrier(0);
         }
-        static_for<NP>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          pk16          x = v[E][k];
-#if HR_PIN_X
-          // opaque: otherwise |x| of pass 1 is kept live (19 more VGPRs) instead of being recomputed
-          asm volatile("" : "+v"(x));
-#endif
-#if HR_KEYS
-          const pk16 f   = pk_nonzero(as_u32(m1[k]) ^ (static_cast<uint32_t>(E) * 0x10001u)); // 0: edge E holds min1
-#else
-          const pk16 f   = pk_min(__builtin_elementwise_abs(x) - m1[k], pk_splat(1)); // 0: this edge holds min1
-#endif
-          const pk16 mag = f * d12[k] + s2[k];
-          const pk16 neg = (sgn[k] ^ x) >> 15;
-          const pk16 c   = (mag ^ neg) - neg;
-          // promotion sum: |c + x| > LLR_MAX is +-SOFT_INF (see edge_pass2)
-          const pk16 out = pk_clamp(c + x, SOFT_INF);
-          c2v.template set<(E0 + E) * NP + k>(c);
-          lds[hr_addr<E0 + E, 0, k * T>(t)]       = static_cast<int8_t>(out.x);
-          lds[hr_addr<E0 + E, HR_HALF, k * T>(t)] = static_cast<int8_t>(out.y);
-        });
+        const pk16 x   = v[E];
+        const pk16 f   = pk_min(__builtin_elementwise_abs(x) - m1, pk_splat(1)); // 0: this edge holds min1
+        const pk16 mag = f * d12 + s2;
+        const pk16 neg = (sgn ^ x) >> 15;
+        const pk16 c   = (mag ^ neg) - neg;
+        // promotion sum: |c + x| > LLR_MAX is +-SOFT_INF (see edge_pass2)
+        const pk16 out = pk_clamp(c + x, SOFT_INF);
+        c2v.template set<E0 + E>(c);
+        lds[hr_addr<E0 + E, 0>(t)]       = static_cast<int8_t>(out.x);
+        lds[hr_addr<E0 + E, HR_HALF>(t)] = static_cast<int8_t>(out.y);
       }(),
       ...);
 }
 
-// hr_layer with the edges taken two at a time (HR_PAIRS=1, an r06 A/B kept for the record, not the default): each
-// packed operation of an edge pair is two independent v_pk_* instructions on a four-element vector (edge a's row
-// pair, edge b's row pair), so consecutive VOP3P instructions of one wave no longer depend on each other and the
-// hazard s_nop between dependent packed instructions goes (878 -> 224 in the headline decoder's code).  The even
-// edges feed the low half's reduction chain and the odd edges the high half's, exactly the two chains of hr_layer,
-// so outputs and iteration counts are identical (decoder and golden tests pass).  Measured slower: 388 vs 345 us
-// per in-step launch (profiles/r06_ldpc_pairs_ab.md) -- the pairs cost 80 extra v_perm_b32 and ~32 VGPRs of
-// scratch spills, and with eight waves per SIMD the nops of one wave were already covered by the others' issue.
-#ifndef HR_PAIRS
-#define HR_PAIRS 0
-#endif
-#ifndef HR_PCHUNK
-#define HR_PCHUNK 3
-#endif
-typedef short pk4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ pk4 pk_cat(pk16 a, pk16 b)
-{
-  return __builtin_shufflevector(a, b, 0, 1, 2, 3);
-}
-__device__ __forceinline__ pk16 pk_lo(pk4 v)
-{
-  return __builtin_shufflevector(v, v, 0, 1);
-}
-__device__ __forceinline__ pk16 pk_hi(pk4 v)
-{
-  return __builtin_shufflevector(v, v, 2, 3);
-}
-__device__ __forceinline__ pk4 pk4_splat(int v)
-{
-  const short x = static_cast<short>(v);
-  return pk4{x, x, x, x};
-}
-__device__ __forceinline__ pk4 pk4_clamp(pk4 x, int lim)
-{
-  return __builtin_elementwise_min(__builtin_elementwise_max(x, pk4_splat(-lim)), pk4_splat(lim));
-}
-
-template <int L, int ARITH, int NP, typename MSGS, int... P>
-__device__ __forceinline__ void hr_layer_pairs(lds_i8* lds, MSGS& c2v, uint32_t t, std::integer_sequence<int, P...>)
-{
-  static_assert(!HR_KEYS, "the paired layer keeps |v2c| minima");
-  constexpr int E0  = row_start<1>(L);
-  constexpr int DEG = bg_traits<1>::deg(L);
-  constexpr int T   = HR_HALF / NP;
-  pk16          v[DEG][NP];
-  pk4           mn1[NP], mn2[NP], sg[NP]; // low half: the even edges' chain, high half: the odd edges'
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    mn1[k] = mn2[k] = pk4_splat(LLR_MAX);
-    sg[k]           = pk4_splat(0);
-  }
-  // pass 1 (ldpc_decoder_impl.cpp:235 / :290): v2c and the check-node statistics
-  (
-      [&] {
-        constexpr int Ea = 2 * P, Eb = 2 * P + 1;
-        if constexpr (P % HR_PCHUNK == 0 && P > 0) {
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        static_for<NP>([&](auto kc) {
-          constexpr int k  = decltype(kc)::value;
-          const pk16    sa = pk16{static_cast<short>(lds[hr_addr<E0 + Ea, 0, k * T>(t)]),
-                               static_cast<short>(lds[hr_addr<E0 + Ea, HR_HALF, k * T>(t)])};
-          if constexpr (Eb < DEG) {
-            const pk16 sb  = pk16{static_cast<short>(lds[hr_addr<E0 + Eb, 0, k * T>(t)]),
-                                 static_cast<short>(lds[hr_addr<E0 + Eb, HR_HALF, k * T>(t)])};
-            const pk4  s   = pk_cat(sa, sb);
-            const pk4  c   = pk_cat(c2v.template get<(E0 + Ea) * NP + k>(), c2v.template get<(E0 + Eb) * NP + k>());
-            const pk4  sat = pk4_clamp(s, LLR_MAX);
-            // infinite soft bits (+-SOFT_INF) push |v2c| beyond 220 (see edge_pass1)
-            const pk4 x  = (s - sat) * pk4_splat(INF_BOOST) + pk4_clamp(s - c, LLR_MAX);
-            const pk4 ax = __builtin_elementwise_abs(x);
-            mn2[k]       = __builtin_elementwise_max(mn1[k], __builtin_elementwise_min(ax, mn2[k]));
-            mn1[k]       = __builtin_elementwise_min(mn1[k], ax);
-            sg[k] ^= x;
-            v[Ea][k] = pk_lo(x);
-            v[Eb][k] = pk_hi(x);
-          } else { // the last edge of an odd degree: the even chain
-            const pk16 sat = pk_clamp(sa, LLR_MAX);
-            const pk16 x = (sa - sat) * pk_splat(INF_BOOST) + pk_clamp(sa - c2v.template get<(E0 + Ea) * NP + k>(), LLR_MAX);
-            const pk16 ax = __builtin_elementwise_abs(x);
-            pk16       a1 = pk_lo(mn1[k]), a2 = pk_lo(mn2[k]);
-            a2            = pk_max(a1, pk_min(ax, a2));
-            a1            = pk_min(a1, ax);
-            mn1[k]        = pk_cat(a1, pk_hi(mn1[k]));
-            mn2[k]        = pk_cat(a2, pk_hi(mn2[k]));
-            sg[k]         = pk_cat(pk_lo(sg[k]) ^ x, pk_hi(sg[k]));
-            v[Ea][k]      = x;
-          }
-        });
-      }(),
-      ...);
-  __builtin_amdgcn_sched_barrier(0);
-  pk4 m1q[NP], s2q[NP], d12q[NP], sgq[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    // merge the two chains: min1 = min(a1, b1), min2 = min(max(a1, b1), min(a2, b2))
-    const pk16 a1 = pk_lo(mn1[k]), b1 = pk_hi(mn1[k]);
-    const pk16 m1  = pk_min(a1, b1);
-    const pk16 mn2v = pk_min(pk_max(a1, b1), pk_min(pk_lo(mn2[k]), pk_hi(mn2[k])));
-    const pk16 s1  = pk_scale<ARITH>(m1);
-    const pk16 s2  = pk_scale<ARITH>(mn2v);
-    const pk16 sgn = pk_lo(sg[k]) ^ pk_hi(sg[k]);
-    m1q[k]         = pk_cat(m1, m1);
-    s2q[k]         = pk_cat(s2, s2);
-    d12q[k]        = pk_cat(s1 - s2, s1 - s2);
-    sgq[k]         = pk_cat(sgn, sgn);
-  }
-  // pass 2 (ldpc_decoder_impl.cpp:310, :270): new message and promotion sum
-  (
-      [&] {
-        constexpr int Ea = 2 * P, Eb = 2 * P + 1;
-        if constexpr (P % HR_PCHUNK == 0 && P > 0) {
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        static_for<NP>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          if constexpr (Eb < DEG) {
-            const pk4 x   = pk_cat(v[Ea][k], v[Eb][k]);
-            const pk4 f   = __builtin_elementwise_min(__builtin_elementwise_abs(x) - m1q[k], pk4_splat(1));
-            const pk4 mag = f * d12q[k] + s2q[k];
-            const pk4 neg = (sgq[k] ^ x) >> 15;
-            const pk4 c   = (mag ^ neg) - neg;
-            // promotion sum: |c + x| > LLR_MAX is +-SOFT_INF (see edge_pass2)
-            const pk4 out = pk4_clamp(c + x, SOFT_INF);
-            c2v.template set<(E0 + Ea) * NP + k>(pk_lo(c));
-            c2v.template set<(E0 + Eb) * NP + k>(pk_hi(c));
-            lds[hr_addr<E0 + Ea, 0, k * T>(t)]       = static_cast<int8_t>(out.x);
-            lds[hr_addr<E0 + Ea, HR_HALF, k * T>(t)] = static_cast<int8_t>(out.y);
-            lds[hr_addr<E0 + Eb, 0, k * T>(t)]       = static_cast<int8_t>(out.z);
-            lds[hr_addr<E0 + Eb, HR_HALF, k * T>(t)] = static_cast<int8_t>(out.w);
-          } else {
-            const pk16 x   = v[Ea][k];
-            const pk16 f   = pk_min(__builtin_elementwise_abs(x) - pk_lo(m1q[k]), pk_splat(1));
-            const pk16 mag = f * pk_lo(d12q[k]) + pk_lo(s2q[k]);
-            const pk16 neg = (pk_lo(sgq[k]) ^ x) >> 15;
-            const pk16 c   = (mag ^ neg) - neg;
-            const pk16 out = pk_clamp(c + x, SOFT_INF);
-            c2v.template set<(E0 + Ea) * NP + k>(c);
-            lds[hr_addr<E0 + Ea, 0, k * T>(t)]       = static_cast<int8_t>(out.x);
-            lds[hr_addr<E0 + Ea, HR_HALF, k * T>(t)] = static_cast<int8_t>(out.y);
-          }
-        });
-      }(),
-      ...);
-}
-
-template <int L, int MAXL, int ARITH, int NP, typename MSGS>
+template <int L, int MAXL, int ARITH, typename MSGS>
 __device__ __forceinline__ void hr_layers(lds_i8* lds, MSGS& c2v, uint32_t t, int nof_layers)
 {
   if constexpr (L < MAXL) {
     if (L < 4 || L < nof_layers) {
       asm volatile("" : "+v"(t));
-      if constexpr (HR_PAIRS && !HR_KEYS) {
-        hr_layer_pairs<L, ARITH, NP>(lds, c2v, t, std::make_integer_sequence<int, (bg_traits<1>::deg(L) + 1) / 2>{});
-      } else {
-        hr_layer<L, ARITH, NP>(lds, c2v, t, std::make_integer_sequence<int, bg_traits<1>::deg(L)>{});
-      }
-      if constexpr (NP == 1) {
-        __syncthreads();
-      } else {
-        // one wave per codeblock: the wave's LDS instructions execute in issue order, so the next layer's
-        // gathers see this layer's scatters of every lane; only the compiler must not move LDS accesses
-        // across the layer boundary (it cannot see the cross-lane dependencies)
-        asm volatile("" ::: "memory");
-      }
+      hr_layer<L, ARITH>(lds, c2v, t, std::make_integer_sequence<int, bg_traits<1>::deg(L)>{});
+      __syncthreads();
     }
-    hr_layers<L + 1, MAXL, ARITH, NP>(lds, c2v, t, nof_layers);
+    hr_layers<L + 1, MAXL, ARITH>(lds, c2v, t, nof_layers);
   }
 }
 
@@ -1246,21 +990,22 @@ __device__ __forceinline__ void hr_layers(lds_i8* lds, MSGS& c2v, uint32_t t, in
 // soft bits).
 // ============================================================================
 
-// compressed state words of BG1 layer l, and the offset of layer l's words
-constexpr int fr_words(int l)
+// compressed state words of layer l of base graph BG, and the offset of layer l's words
+template <int BG>
+constexpr int pk_words(int l)
 {
-  return bg_traits<1>::deg(l) > 13 ? 3 : 2;
+  return bg_traits<BG>::deg(l) > 13 ? 3 : 2;
 }
-constexpr int fr_off(int l)
+template <int BG>
+constexpr int pk_off(int l)
 {
   int s = 0;
   for (int i = 0; i < l; ++i) {
-    s += fr_words(i);
+    s += pk_words<BG>(i);
   }
   return s;
 }
-constexpr int FR_STATE_WORDS = fr_off(bg_traits<1>::M);
-static_assert(FR_STATE_WORDS == 96, "BG1 compressed message state");
+static_assert(pk_off<1>(46) == 96 && pk_off<2>(42) == 84, "compressed message state");
 // word and bit (of each 16-bit half) holding the sign of edge e of a row
 constexpr int fr_sign_word(int e)
 {
@@ -1271,20 +1016,9 @@ constexpr int fr_sign_bit(int e)
   return e < 4 ? 12 + e : (e < 13 ? e + 3 : e - 13);
 }
 
-// v_pk_mad_u16 as opaque asm for the old-message magnitude and the argmin key (fewer instructions; 1 = on)
-#ifndef FR_ASM_MAD
-#define FR_ASM_MAD 1
-#endif
-#ifndef FR_SIGN_SHIFT
-#define FR_SIGN_SHIFT 1
-#endif
-#ifndef FR_KEEP_ADDR
-#define FR_KEEP_ADDR 19
-#endif
-
-// compressed message state of the first NW / (2 or 3) layers (all 46: fr_state)
+// compressed message state, NW words (all layers of base graph BG: pk_off<BG>(M))
 template <int NW>
-struct fr_state_n {
+struct pk_state {
   uint32_t w[NW];
   __device__ __forceinline__ void zero()
   {
@@ -1294,21 +1028,50 @@ struct fr_state_n {
     }
   }
 };
-using fr_state = fr_state_n<FR_STATE_WORDS>;
 
-// One layer (BG1 row L) for the row pair of lane t, messages rebuilt from / folded into the compressed state.
-template <int L, int ARITH, typename ST, int... E>
-__device__ __forceinline__ void fr_layer(lds_i8* lds, ST& st, uint32_t t, std::integer_sequence<int, E...>)
+// Where the two soft bits of an edge live is the one thing in which a layer of the full-length kernel and of the
+// packed runtime-Z kernel differ, so pk_layer takes it as a policy POS:
+//   gather<BG, EI>(lds, t, lo, hi)  the soft bits of rows t and t + H of edge EI, and their LDS positions lo, hi
+//                                   (the order of position arithmetic and loads is the policy's: the compiler's
+//                                   schedule of each kernel follows it),
+//   node<BG, EI>()                  a literal added to both positions in the ds instruction,
+//   keep(deg)                       whether a row of that degree holds lo, hi for the scatter or computes them
+//                                   again with rows<EI>(t, lo, hi).
+// Z = 384: positions at compile-time shifts off the lane index (hr_addr), nothing worth recomputing.
+struct pos_z384 {
+  template <int BG, int EI>
+  static constexpr uint32_t node()
+  {
+    return 0;
+  }
+  static constexpr bool keep(int) { return true; }
+  template <int BG, int EI>
+  __device__ __forceinline__ pk16 gather(lds_i8* lds, uint32_t t, uint32_t& lo, uint32_t& hi) const
+  {
+    lo            = hr_addr<EI, 0>(t);
+    const short a = lds[lo];
+    hi            = hr_addr<EI, HR_HALF>(t);
+    return pk16{a, static_cast<short>(lds[hi])};
+  }
+};
+
+// One layer (row L of base graph BG) for the row pair of lane t, messages rebuilt from / folded into the
+// compressed state.
+template <int BG, int L, int ARITH, typename POS, typename ST, int... E>
+__device__ __forceinline__ void pk_layer(lds_i8* lds, ST& st, uint32_t t, const POS& pos,
+                                         std::integer_sequence<int, E...>)
 {
-  constexpr int  E0  = row_start<1>(L);
-  constexpr int  DEG = sizeof...(E);
-  constexpr int  O   = fr_off(L);
-  constexpr bool W3  = fr_words(L) == 3;
+  constexpr int  E0   = row_start<BG>(L);
+  constexpr int  DEG  = sizeof...(E);
+  constexpr int  O    = pk_off<BG>(L);
+  constexpr bool W3   = pk_words<BG>(L) == 3;
+  constexpr bool KEEP = POS::keep(DEG);
   const uint32_t wold[3] = {st.w[O], st.w[O + 1], W3 ? st.w[O + 2] : 0u};
   const pk16     s2o     = as_pk(wold[0] & 0x007f007fu);
   const uint32_t imo     = wold[0] & 0x0f800f80u;
   const pk16     dno     = pk_splat(0) - as_pk(wold[1] & 0x007f007fu); // s1 - s2 of the old messages
   pk16           v[DEG];
+  uint32_t       plo[KEEP ? DEG : 1], phi[KEEP ? DEG : 1];
   pk16           min1[2], min2[2];
   pk16           sgn = pk_splat(0);
   // keys |v2c| << 5 | e; the initial key stands for the reference's LLR_MAX start value (no edge index)
@@ -1320,25 +1083,22 @@ __device__ __forceinline__ void fr_layer(lds_i8* lds, ST& st, uint32_t t, std::i
           __builtin_amdgcn_sched_barrier(0);
         }
         constexpr int h = E & 1; // reduction chain
-        const pk16    s = pk16{static_cast<short>(lds[hr_addr<E0 + E, 0>(t)]),
-                            static_cast<short>(lds[hr_addr<E0 + E, HR_HALF>(t)])};
+        uint32_t      lo, hi;
+        const pk16    s = pos.template gather<BG, E0 + E>(lds, t, lo, hi);
+        if constexpr (KEEP) {
+          plo[E] = lo;
+          phi[E] = hi;
+        }
         // old message: +-(e == idx ? s2 : s1)
         const pk16 f   = pk_nonzero(imo ^ ((static_cast<uint32_t>(E) << 7) * 0x10001u));
-#if FR_ASM_MAD
+        // magnitude and argmin key as opaque v_pk_mad_u16 (fewer instructions than the compiler's own)
         const pk16 mag = pk_mad(f, dno, s2o);
-#else
-        const pk16 mag = f * dno + s2o;
-#endif
         const pk16 ng  = (as_pk(wold[fr_sign_word(E)]) << pk_splat(15 - fr_sign_bit(E))) >> 15;
         const pk16 c   = (mag ^ ng) - ng;
         const pk16 sat = pk_clamp(s, LLR_MAX);
         // infinite soft bits (+-SOFT_INF) push |v2c| beyond 220 (see edge_pass1)
         const pk16 x   = (s - sat) * pk_splat(INF_BOOST) + pk_clamp(s - c, LLR_MAX);
-#if FR_ASM_MAD
         const pk16 key = pk_key<E>(__builtin_elementwise_abs(x));
-#else
-        const pk16 key = __builtin_elementwise_abs(x) * pk_splat(32) + pk_splat(E);
-#endif
         min2[h]        = pk_max(min1[h], pk_min(key, min2[h])); // median(min1, key, min2)
         min1[h]        = pk_min(min1[h], key);
         sgn ^= x;
@@ -1353,8 +1113,8 @@ __device__ __forceinline__ void fr_layer(lds_i8* lds, ST& st, uint32_t t, std::i
   const pk16     d12 = s1 - s2;
   const uint32_t idx = as_u32(k1) & 0x001f001fu;
   uint32_t       acc[3] = {(idx << 7) | as_u32(s2), as_u32(s2 - s1), 0u};
-  if constexpr (DEG > FR_KEEP_ADDR) {
-    // rows of high degree recompute their scatter addresses instead of holding DEG of them live
+  if constexpr (!KEEP) {
+    // the scatter positions are computed again instead of holding DEG pairs of them live
     asm volatile("" : "+v"(t));
   }
   // pass 2 (ldpc_decoder_impl.cpp:310, :270): new message, promotion sum, new state
@@ -1363,6 +1123,7 @@ __device__ __forceinline__ void fr_layer(lds_i8* lds, ST& st, uint32_t t, std::i
         if constexpr (E % HR_CHUNK2 == 0 && E > 0) {
           __builtin_amdgcn_sched_barrier(0);
         }
+        constexpr uint32_t node = POS::template node<BG, E0 + E>();
         const pk16 x   = v[E];
         const pk16 f   = pk_nonzero(idx ^ (static_cast<uint32_t>(E) * 0x10001u)); // 0: this edge holds min1
         const pk16 mag = f * d12 + s2;
@@ -1371,16 +1132,18 @@ __device__ __forceinline__ void fr_layer(lds_i8* lds, ST& st, uint32_t t, std::i
         const pk16 c   = (mag ^ ng) - ng;
         // promotion sum: |c + x| > LLR_MAX is +-SOFT_INF (see edge_pass2)
         const pk16 out = pk_clamp(c + x, SOFT_INF);
-#if FR_SIGN_SHIFT
         // sign bit into both halves of the state word: (sx >>> 15) << bit, one v_lshl_or_b32 with an inline shift
         const uint32_t nb = __builtin_bit_cast(uint32_t, __builtin_bit_cast(pku16, sx) >> 15);
         acc[fr_sign_word(E)] |= nb << fr_sign_bit(E);
-#else
-        // sign mask of both halves into the state word: one v_and_or_b32 (mask constant in an SGPR)
-        acc[fr_sign_word(E)] |= as_u32(ng) & ((1u << fr_sign_bit(E)) * 0x10001u);
-#endif
-        lds[hr_addr<E0 + E, 0>(t)]       = static_cast<int8_t>(out.x);
-        lds[hr_addr<E0 + E, HR_HALF>(t)] = static_cast<int8_t>(out.y);
+        uint32_t lo, hi;
+        if constexpr (KEEP) {
+          lo = plo[E];
+          hi = phi[E];
+        } else {
+          pos.template rows<E0 + E>(t, lo, hi);
+        }
+        lds[lo + node] = static_cast<int8_t>(out.x);
+        lds[hi + node] = static_cast<int8_t>(out.y);
       }(),
       ...);
   // pin the assembled words here: left alone the compiler sinks the sign-bit ORs past the layer's join and
@@ -1398,9 +1161,6 @@ __device__ __forceinline__ void fr_layer(lds_i8* lds, ST& st, uint32_t t, std::i
 // bits, so no workgroup barrier is needed between them -- the result is the sequential one, bit for bit.  A layer
 // starts a new group when one of its columns is a column of a layer of the current group.  BG1 (the lower part is
 // built of orthogonal row pairs): 32 groups for 46 layers, layers 16-17, 20-21, 22-23, ..., 44-45 paired.
-#ifndef FR_GROUPS
-#define FR_GROUPS 1
-#endif
 template <int BG>
 struct bg_groups_t {
   int first[bg_traits<BG>::M] = {}; // first layer of the group of layer l
@@ -1452,9 +1212,9 @@ __device__ __forceinline__ void fr_layers(lds_i8* lds, ST& st, uint32_t t, int n
     asm volatile("" : "+s"(nof_layers));
     if (L < 4 || L < nof_layers) { // uniform; nof_layers >= 4
       asm volatile("" : "+v"(t));
-      fr_layer<L, ARITH>(lds, st, t, std::make_integer_sequence<int, bg_traits<1>::deg(L)>{});
+      pk_layer<1, L, ARITH>(lds, st, t, pos_z384{}, std::make_integer_sequence<int, bg_traits<1>::deg(L)>{});
       // a barrier before the next layer unless it continues this one's group (and runs); always one after the last
-      constexpr bool next_joins = FR_GROUPS && L + 1 < MAXL && bg1_group_start(L + 1) != L + 1;
+      constexpr bool next_joins = L + 1 < MAXL && bg1_group_start(L + 1) != L + 1;
       if (!next_joins || !(L + 1 < 4 || L + 1 < nof_layers)) {
         __syncthreads();
       } else {
@@ -1465,30 +1225,14 @@ __device__ __forceinline__ void fr_layers(lds_i8* lds, ST& st, uint32_t t, int n
   }
 }
 
-// NP row pairs per lane: NP = 1 -> 192 threads (3 waves) per codeblock, NP = 3 -> one wave per codeblock
-// (no workgroup barriers, three independent pair streams per lane).
-#ifndef HR_WAVES
-#define HR_WAVES 4
-#endif
-#ifndef FR_WAVES
-#define FR_WAVES 3
-#endif
-// HR_CMP: the high-rate kernel holds its MAXL layers' messages compressed (fr_layer) instead of as int16 pairs
-#ifndef HR_CMP
-#define HR_CMP 0
-#endif
-// HR_OLD_LOAD: the codeword-fed load deinterleaves raw bytes and clamps / completes / scans the row in a second pass
-// (r05 form, kept for A/B)
-#ifndef HR_OLD_LOAD
-#define HR_OLD_LOAD 0
-#endif
-#ifndef HR_CMP_WAVES
-#define HR_CMP_WAVES 8
-#endif
-template <int NP, int MAXL>
+// Occupancy targets (waves per SIMD) of the high-rate and the full-length kernel; a codeblock is 192 threads
+// (3 waves) in both.
+constexpr int HR_WAVES = 4;
+constexpr int FR_WAVES = 3;
+template <int MAXL>
 constexpr int hr_waves_per_simd()
 {
-  return MAXL == bg_traits<1>::M ? FR_WAVES : (NP == 1 ? (HR_CMP ? HR_CMP_WAVES : HR_WAVES) : 2);
+  return MAXL == bg_traits<1>::M ? FR_WAVES : HR_WAVES;
 }
 
 // threadIdx.x rebuilt from the wave's first thread (wave-uniform) and the lane id: opaque (volatile), so it is
@@ -1503,17 +1247,17 @@ __device__ __forceinline__ uint32_t hr_thread(uint32_t wave_base)
 // MAXL < 46: the high-rate kernel (int16 messages of the first MAXL layers in registers); MAXL == 46: the
 // full-length kernel (compressed messages of every layer).
 template <int ARITH, int MAXL, int NP>
-__global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>())) ldpc_decode_hr_kernel(decode_args a)
+__global__ void __launch_bounds__(HR_HALF, (hr_waves_per_simd<MAXL>())) ldpc_decode_hr_kernel(decode_args a)
 {
-  constexpr bool FULL   = MAXL == bg_traits<1>::M;
-  constexpr bool CMP    = FULL || (HR_CMP && NP == 1); // compressed message state
-  static_assert(!FULL || NP == 1, "full-length codeblocks: one row pair per lane");
+  // NP (row pairs per lane) is always 1: it stays because benchmarks and committed profiles key on the kernel's name
+  static_assert(NP == 1, "one row pair per lane");
+  constexpr bool FULL   = MAXL == bg_traits<1>::M; // compressed message state
   constexpr int Z       = HR_Z;
   constexpr int K       = 22 * Z;
   constexpr int NODES   = 22 + MAXL;
-  constexpr int NE      = row_start<1>(MAXL) * NP;
+  constexpr int NE      = row_start<1>(MAXL);
   constexpr int MAX_LLR = (NODES - 2) * Z; // host guarantees llr_len <= MAX_LLR
-  constexpr int NT      = HR_HALF / NP;
+  constexpr int NT      = HR_HALF;
   lds_i32*      red     = (lds_i32*)(uintptr_t)LDS_RED_OFFSET;
   lds_i8*       lds     = (lds_i8*)(uintptr_t)0;
   lds_i8*       soft    = lds + LDS_SOFT_OFFSET;
@@ -1538,14 +1282,12 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
 
     // ---- input scan (last non-zero LLR, ldpc_decoder_impl.cpp:86) fused with the soft-bit load
     // (:160): clamped full nodes, the partial tail node unclamped, zeros elsewhere.
-    if constexpr (NT > 64) {
-      if (t == 0) {
-        red[0] = -1;
-        red[1] = 0;
-        red[2] = 0;
-      }
-      __syncthreads();
+    if (t == 0) {
+      red[0] = -1;
+      red[1] = 0;
+      red[2] = 0;
     }
+    __syncthreads();
     int input_size;
     if (a.cw_llrs != nullptr) {
       // ---- rate dematching fused into the load (decode_args::cw_llrs): the codeblock's E received LLRs are
@@ -1559,7 +1301,7 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
       const uint32_t ninfo = a.cw_nof_info;
       const uint32_t F     = a.cw_filler;
       lds_i8*        row   = soft + 2 * Z;
-      if (Qm == 8 && ((reinterpret_cast<uintptr_t>(src) & 7u) == 0) && n_llrs % Z == 0 && !HR_OLD_LOAD) {
+      if (Qm == 8 && ((reinterpret_cast<uintptr_t>(src) & 7u) == 0) && n_llrs % Z == 0) {
         // Whole nodes only (the fused launches' prefix is whole nodes): every byte of the row is a full-node soft
         // bit, clamped to +-SOFT_CLAMP as it is stored, so the row needs no second pass.  Fillers (+infinity)
         // are stored as +SOFT_CLAMP and the bytes from E + F on as zeros (disjoint from the deinterleaved bytes,
@@ -1634,15 +1376,11 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
               last = 4 * w + (31 - __builtin_clz(v)) / 8;
             }
           }
-          if constexpr (NT == 64) {
-            input_size = __builtin_amdgcn_readfirstlane(wave_max(last) + 1);
-          } else {
-            if (last >= 0) {
-              __hip_atomic_fetch_max(&red[0], last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            __syncthreads();
-            input_size = __builtin_amdgcn_readfirstlane(red[0] + 1);
+          if (last >= 0) {
+            __hip_atomic_fetch_max(&red[0], last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           }
+          __syncthreads();
+          input_size = __builtin_amdgcn_readfirstlane(red[0] + 1);
         } else {
           // MAXL layers whatever the last non-zero position (<= (NODES - 2) Z): cb_len below gives MAXL
           input_size = n_llrs;
@@ -1701,15 +1439,11 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
       for (int w = t; w < 2 * Z / 4; w += NT) {
         soft4[w] = 0;
       }
-      if constexpr (NT == 64) {
-        input_size = __builtin_amdgcn_readfirstlane(wave_max(last) + 1);
-      } else {
-        if (last >= 0) {
-          __hip_atomic_fetch_max(&red[0], last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        __syncthreads();
-        input_size = __builtin_amdgcn_readfirstlane(red[0] + 1);
+      if (last >= 0) {
+        __hip_atomic_fetch_max(&red[0], last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
+      __syncthreads();
+      input_size = __builtin_amdgcn_readfirstlane(red[0] + 1);
       }
     } else {
       const int      nw  = n_llrs >> 2;
@@ -1752,15 +1486,11 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
       for (int w = t; w < 2 * Z / 4; w += NT) {
         soft4[w] = 0;
       }
-      if constexpr (NT == 64) {
-        input_size = __builtin_amdgcn_readfirstlane(wave_max(last) + 1);
-      } else {
-        if (last >= 0) {
-          __hip_atomic_fetch_max(&red[0], last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        __syncthreads();
-        input_size = __builtin_amdgcn_readfirstlane(red[0] + 1);
+      if (last >= 0) {
+        __hip_atomic_fetch_max(&red[0], last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
+      __syncthreads();
+      input_size = __builtin_amdgcn_readfirstlane(red[0] + 1);
     }
 
     if (input_size < K && a.force_decoding) {
@@ -1772,9 +1502,7 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
       if (tf == 0) {
         a.nof_iters[cb] = -1;
       }
-      if constexpr (NT > 64) {
-        __syncthreads();
-      }
+      __syncthreads();
       continue;
     }
     const int cb_len     = max(input_size + 2 * Z, K + 4 * Z);
@@ -1783,14 +1511,14 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
     const int nof_sig    = __builtin_amdgcn_readfirstlane(K - (a.fillers ? a.fillers[cb] : a.nof_filler_bits));
     int       result     = -1;
 
-    std::conditional_t<CMP, fr_state_n<fr_off(MAXL)>, hr_msgs<NE>> c2v;
+    std::conditional_t<FULL, pk_state<pk_off<1>(MAXL)>, hr_msgs<NE>> c2v;
     c2v.zero();
 
     for (int it = 0; it < a.max_iterations; ++it) {
-      if constexpr (CMP) {
+      if constexpr (FULL) {
         fr_layers<0, ARITH, MAXL>(lds, c2v, t, nof_layers);
       } else {
-        hr_layers<0, MAXL, ARITH, NP>(lds, c2v, t, nof_layers);
+        hr_layers<0, MAXL, ARITH>(lds, c2v, t, nof_layers);
       }
 
       if (a.crc_table) {
@@ -1831,16 +1559,6 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
               crc ^= a.crc_table[K - 1 - (4 * q + b)];
             }
           }
-        }
-        if constexpr (NT == 64) {
-          // one wave: shuffle reductions, no LDS round trip and no barrier
-          const uint32_t c_all = __builtin_amdgcn_readfirstlane(wave_xor(crc));
-          const uint32_t z_all = __builtin_amdgcn_readfirstlane(wave_or(zero));
-          if (z_all == 0 && c_all == 0) {
-            result = it + 1;
-            break;
-          }
-          continue;
         }
         lds_u32* acc = reinterpret_cast<lds_u32*>(&red[1 + 2 * (it & 1)]);
         if (crc != 0) {
@@ -1903,11 +1621,7 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
     if (te == 0) {
       a.nof_iters[cb] = result;
     }
-    if constexpr (NT > 64) {
-      __syncthreads();
-    } else {
-      asm volatile("" ::: "memory"); // the next codeblock's soft-bit stores follow this one's reads
-    }
+    __syncthreads();
   }
 }
 
@@ -1921,39 +1635,11 @@ __global__ void __launch_bounds__(HR_HALF / NP, (hr_waves_per_simd<NP, MAXL>()))
 //   * soft bits in LDS at a compile-time stride of 128 W bytes per variable node, so the node offset of an
 //     edge is a literal in the ds instruction's immediate, and only (row + shift) mod Z is computed per row:
 //     two adds and a min on the lane index, the shift and shift - Z coming from the scalar unit;
-//   * the compressed messages of every layer in registers (fr_layer): BG1 96 VGPRs, BG2 84;
+//   * the compressed messages of every layer in registers (pk_layer): BG1 96 VGPRs, BG2 84;
 //   * the LLR row, the CRC and the hard decision address the node-strided LDS through i / Z computed as
 //     umulhi(i, ceil(2^32 / Z)) (exact for i < 2^16).
 // Bit-exact with ldpc_decode_kernel (same per-edge arithmetic; identical outputs, iteration counts, soft bits).
 // ============================================================================
-
-template <int BG>
-constexpr int pk_words(int l)
-{
-  return bg_traits<BG>::deg(l) > 13 ? 3 : 2;
-}
-template <int BG>
-constexpr int pk_off(int l)
-{
-  int s = 0;
-  for (int i = 0; i < l; ++i) {
-    s += pk_words<BG>(i);
-  }
-  return s;
-}
-static_assert(pk_off<1>(46) == FR_STATE_WORDS && pk_off<2>(42) == 84, "compressed message state");
-
-template <int BG>
-struct pk_state {
-  uint32_t w[pk_off<BG>(bg_traits<BG>::M)];
-  __device__ __forceinline__ void zero()
-  {
-#pragma unroll
-    for (int i = 0; i < pk_off<BG>(bg_traits<BG>::M); ++i) {
-      w[i] = 0;
-    }
-  }
-};
 
 // base-graph variable node of edge E (compile time)
 template <int BG, int E>
@@ -1980,103 +1666,31 @@ __device__ __forceinline__ void pk_rows(const pk_geo& g, uint32_t t, uint32_t& l
 }
 
 // rows of degree <= PK_KEEP_ADDR keep their gather positions for the scatter; longer rows recompute them
-#ifndef PK_KEEP_ADDR
-#define PK_KEEP_ADDR 10
-#endif
+constexpr int PK_KEEP_ADDR = 10;
 
-// One layer (row L of base graph BG) for the row pair of lane t (fr_layer with run-time positions).
-template <int BG, int L, int ARITH, int STRIDE, int... E>
-__device__ __forceinline__ void pk_layer(lds_i8* lds, pk_state<BG>& st, uint32_t t, const pk_geo& g,
-                                         std::integer_sequence<int, E...>)
-{
-  constexpr int  E0   = row_start<BG>(L);
-  constexpr int  DEG  = sizeof...(E);
-  constexpr int  O    = pk_off<BG>(L);
-  constexpr bool W3   = pk_words<BG>(L) == 3;
-  constexpr bool KEEP = DEG <= PK_KEEP_ADDR;
-  const uint32_t wold[3] = {st.w[O], st.w[O + 1], W3 ? st.w[O + 2] : 0u};
-  const pk16     s2o     = as_pk(wold[0] & 0x007f007fu);
-  const uint32_t imo     = wold[0] & 0x0f800f80u;
-  const pk16     dno     = pk_splat(0) - as_pk(wold[1] & 0x007f007fu); // s1 - s2 of the old messages
-  pk16           v[DEG];
-  uint32_t       plo[KEEP ? DEG : 1], phi[KEEP ? DEG : 1];
-  pk16           min1[2], min2[2];
-  pk16           sgn = pk_splat(0);
-  min1[0] = min1[1] = min2[0] = min2[1] = pk_splat(LLR_MAX * 32 + 31);
-  // pass 1 (ldpc_decoder_impl.cpp:235 / :290): old message, v2c, check-node statistics
-  (
-      [&] {
-        if constexpr (E % HR_CHUNK1 == 0 && E > 0) {
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        constexpr int      h    = E & 1; // reduction chain
-        constexpr uint32_t node = LDS_SOFT_OFFSET + bg_var<BG, E0 + E>() * STRIDE;
-        uint32_t           lo, hi;
-        pk_rows<E0 + E>(g, t, lo, hi);
-        if constexpr (KEEP) {
-          plo[E] = lo;
-          phi[E] = hi;
-        }
-        const pk16 s   = pk16{static_cast<short>(lds[lo + node]), static_cast<short>(lds[hi + node])};
-        const pk16 f   = pk_nonzero(imo ^ ((static_cast<uint32_t>(E) << 7) * 0x10001u));
-        const pk16 mag = pk_mad(f, dno, s2o);
-        const pk16 ng  = (as_pk(wold[fr_sign_word(E)]) << pk_splat(15 - fr_sign_bit(E))) >> 15;
-        const pk16 c   = (mag ^ ng) - ng;
-        const pk16 sat = pk_clamp(s, LLR_MAX);
-        const pk16 x   = (s - sat) * pk_splat(INF_BOOST) + pk_clamp(s - c, LLR_MAX);
-        const pk16 key = pk_key<E>(__builtin_elementwise_abs(x));
-        min2[h]        = pk_max(min1[h], pk_min(key, min2[h])); // median(min1, key, min2)
-        min1[h]        = pk_min(min1[h], key);
-        sgn ^= x;
-        v[E] = x;
-      }(),
-      ...);
-  __builtin_amdgcn_sched_barrier(0);
-  const pk16     k1     = pk_min(min1[0], min1[1]);
-  const pk16     k2     = pk_min(pk_max(min1[0], min1[1]), pk_min(min2[0], min2[1]));
-  const pk16     s1     = pk_scale16<ARITH>(k1 >> 5);
-  const pk16     s2     = pk_scale16<ARITH>(k2 >> 5);
-  const pk16     d12    = s1 - s2;
-  const uint32_t idx    = as_u32(k1) & 0x001f001fu;
-  uint32_t       acc[3] = {(idx << 7) | as_u32(s2), as_u32(s2 - s1), 0u};
-  if constexpr (!KEEP) {
-    asm volatile("" : "+v"(t));
+// pk_layer's soft-bit positions for a run-time Z: (row + shift) mod Z from the codeblock's lifted graph, the
+// variable node (STRIDE bytes each) as the literal.
+template <int STRIDE>
+struct pos_runtime {
+  const pk_geo& g;
+  template <int BG, int EI>
+  static constexpr uint32_t node()
+  {
+    return LDS_SOFT_OFFSET + bg_var<BG, EI>() * STRIDE;
   }
-  // pass 2 (ldpc_decoder_impl.cpp:310, :270): new message, promotion sum, new state
-  (
-      [&] {
-        if constexpr (E % HR_CHUNK2 == 0 && E > 0) {
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        constexpr uint32_t node = LDS_SOFT_OFFSET + bg_var<BG, E0 + E>() * STRIDE;
-        const pk16         x    = v[E];
-        const pk16         f    = pk_nonzero(idx ^ (static_cast<uint32_t>(E) * 0x10001u)); // 0: edge E holds min1
-        const pk16         mag  = f * d12 + s2;
-        const pk16         sx   = sgn ^ x;
-        const pk16         ng   = sx >> 15;
-        const pk16         c    = (mag ^ ng) - ng;
-        const pk16         out  = pk_clamp(c + x, SOFT_INF);
-        const uint32_t     nb   = __builtin_bit_cast(uint32_t, __builtin_bit_cast(pku16, sx) >> 15);
-        acc[fr_sign_word(E)] |= nb << fr_sign_bit(E);
-        uint32_t lo, hi;
-        if constexpr (KEEP) {
-          lo = plo[E];
-          hi = phi[E];
-        } else {
-          pk_rows<E0 + E>(g, t, lo, hi);
-        }
-        lds[lo + node] = static_cast<int8_t>(out.x);
-        lds[hi + node] = static_cast<int8_t>(out.y);
-      }(),
-      ...);
-  asm volatile("" : "+v"(acc[0]), "+v"(acc[1]));
-  st.w[O]     = acc[0];
-  st.w[O + 1] = acc[1];
-  if constexpr (W3) {
-    asm volatile("" : "+v"(acc[2]));
-    st.w[O + 2] = acc[2];
+  static constexpr bool keep(int deg) { return deg <= PK_KEEP_ADDR; }
+  template <int EI>
+  __device__ __forceinline__ void rows(uint32_t t, uint32_t& lo, uint32_t& hi) const
+  {
+    pk_rows<EI>(g, t, lo, hi);
   }
-}
+  template <int BG, int EI>
+  __device__ __forceinline__ pk16 gather(lds_i8* lds, uint32_t t, uint32_t& lo, uint32_t& hi) const
+  {
+    rows<EI>(t, lo, hi);
+    return pk16{static_cast<short>(lds[lo + node<BG, EI>()]), static_cast<short>(lds[hi + node<BG, EI>()])};
+  }
+};
 
 // own: the lane owns its row pair (threadIdx.x < H).  A repeating lane (t >= H, rows of lane t mod H) sits in another
 // wave than its owner when H is not a multiple of 64 (Z = 136..252 or 264..380 with Z / 2 mod 64 != 0): with no
@@ -2084,8 +1698,8 @@ __device__ __forceinline__ void pk_layer(lds_i8* lds, pk_state<BG>& st, uint32_t
 // repeating wave gathers them, which then computes -- and scatters -- different values (BG2 Z = 288 soft bits
 // differed in 0.6 % of positions, intermittently).  Repeating lanes therefore skip the layers: they only fill the
 // workgroup for the CRC, hard-decision and export loops, which index words by threadIdx.x.
-template <int BG, int L, int ARITH, int W>
-__device__ __forceinline__ void pk_layers(lds_i8* lds, pk_state<BG>& st, uint32_t t, pk_geo g, int nof_layers, bool own)
+template <int BG, int L, int ARITH, int W, typename ST>
+__device__ __forceinline__ void pk_layers(lds_i8* lds, ST& st, uint32_t t, pk_geo g, int nof_layers, bool own)
 {
   if constexpr (L < bg_traits<BG>::M) {
     asm volatile("" : "+s"(nof_layers));
@@ -2093,11 +1707,12 @@ __device__ __forceinline__ void pk_layers(lds_i8* lds, pk_state<BG>& st, uint32_
       // laundered per layer: the positions are iteration-invariant, hoisted they would spill
       asm volatile("" : "+v"(t), "+s"(g.edge), "+s"(g.Z), "+s"(g.H));
       if (own) {
-        pk_layer<BG, L, ARITH, 128 * W>(lds, st, t, g, std::make_integer_sequence<int, bg_traits<BG>::deg(L)>{});
+        pk_layer<BG, L, ARITH>(lds, st, t, pos_runtime<128 * W>{g},
+                               std::make_integer_sequence<int, bg_traits<BG>::deg(L)>{});
       }
       // no barrier before a next layer of the same group (disjoint columns, see bg_groups_t); always one after
       // the last layer that runs
-      constexpr bool next_joins = FR_GROUPS && L + 1 < bg_traits<BG>::M && bg_group_start<BG>(L + 1) != L + 1;
+      constexpr bool next_joins = L + 1 < bg_traits<BG>::M && bg_group_start<BG>(L + 1) != L + 1;
       if constexpr (W > 1) {
         if (!next_joins || !(L + 1 < 4 || L + 1 < nof_layers)) {
           __syncthreads();
@@ -2112,12 +1727,9 @@ __device__ __forceinline__ void pk_layers(lds_i8* lds, pk_state<BG>& st, uint32_
   }
 }
 
-#ifndef PK_WAVES_BG1
-#define PK_WAVES_BG1 3
-#endif
-#ifndef PK_WAVES_BG2
-#define PK_WAVES_BG2 3
-#endif
+// occupancy target (waves per SIMD) of the packed kernel per base graph
+constexpr int PK_WAVES_BG1 = 3;
+constexpr int PK_WAVES_BG2 = 3;
 
 __host__ __device__ constexpr int pk_lds_bytes(int bg, int w)
 {
@@ -2246,7 +1858,7 @@ __global__ void __launch_bounds__(64 * W, (BG == 1 ? PK_WAVES_BG1 : PK_WAVES_BG2
     const pk_geo   geo{(const_u32_ptr)(a.edges + e_off), Z, H};
     const uint32_t tr         = t < H ? t : t % H; // the row pair of this lane (lanes t >= H repeat one)
 
-    pk_state<BG> st;
+    pk_state<pk_off<BG>(bg_traits<BG>::M)> st;
     st.zero();
 
     for (int it = 0; it < a.max_iterations; ++it) {
@@ -2343,13 +1955,18 @@ __global__ void __launch_bounds__(64 * W, (BG == 1 ? PK_WAVES_BG1 : PK_WAVES_BG2
   }
 }
 
+// A run-time switch of the kernel selection: on unless the variable starts with '0'.
+static bool env_enabled(const char* name)
+{
+  const char* e = std::getenv(name);
+  return e == nullptr || e[0] != '0';
+}
+
 // Waves per codeblock of the packed kernel for a lifting size, 0 when it does not take it.
 int ldpc_pk_waves(int bg, int Z)
 {
   // read per call (A/B timing and the parity tests switch it per launch)
-  const char* mode    = std::getenv("SRSRAN_AMD_LDPC_PK");
-  const bool  enabled = mode == nullptr || mode[0] != '0';
-  if (!enabled || (bg != 1 && bg != 2) || Z < 4 || (Z & 3) != 0 || Z > MAX_LIFTING_SIZE) {
+  if (!env_enabled("SRSRAN_AMD_LDPC_PK") || (bg != 1 && bg != 2) || Z < 4 || (Z & 3) != 0 || Z > MAX_LIFTING_SIZE) {
     return 0;
   }
   return (Z / 2 + 63) / 64;
@@ -2377,18 +1994,11 @@ static void launch_pk(const decode_args& args, int W, uint32_t Z, int grid, hipS
 }
 
 constexpr int HR_MAXL = 4;
-#ifndef HR_NP_DEFAULT
-#define HR_NP_DEFAULT 1
-#endif
-constexpr int HR_NP = HR_NP_DEFAULT; // row pairs per lane (1: three waves per codeblock, 3: one wave)
 
 bool ldpc_decode_hr_eligible(const decode_args& args, const lifted_graph& g)
 {
   // SRSRAN_AMD_LDPC_HR=0 keeps every launch on ldpc_decode_kernel (A/B timing, cross-checks).
-  static const bool enabled = [] {
-    const char* e = std::getenv("SRSRAN_AMD_LDPC_HR");
-    return e == nullptr || e[0] != '0';
-  }();
+  static const bool enabled = env_enabled("SRSRAN_AMD_LDPC_HR");
   return enabled && g.bg == 1 && g.Z == HR_Z && args.llr_lens == nullptr && args.aligned4 != 0 &&
          args.llr_len <= static_cast<uint32_t>((20 + HR_MAXL) * HR_Z) &&
          ((reinterpret_cast<uintptr_t>(args.soft_out) | (args.soft_out ? 68u * HR_Z : 0u)) & 3u) == 0;
@@ -2445,10 +2055,7 @@ static void launch_bg(const decode_args& args, const lifted_graph& g, int grid, 
 
 bool ldpc_hr_takes(int bg, int Z, uint32_t llr_len)
 {
-  static const bool enabled = [] {
-    const char* e = std::getenv("SRSRAN_AMD_LDPC_HR");
-    return e == nullptr || e[0] != '0';
-  }();
+  static const bool enabled = env_enabled("SRSRAN_AMD_LDPC_HR");
   return enabled && bg == 1 && Z == HR_Z && llr_len <= static_cast<uint32_t>((20 + HR_MAXL) * HR_Z) &&
          (llr_len & 3u) == 0;
 }
@@ -2461,14 +2068,13 @@ hipError_t launch_ldpc_decode(const decode_args& args, const lifted_graph& g, in
   if (ldpc_decode_hr_eligible(args, g)) {
     // The crc table of the high-rate kernel is indexed from K Z - 1 down, 16-byte aligned.
     constexpr size_t lds = hr_lds_bytes<HR_MAXL>();
-    constexpr int    NT  = HR_HALF / HR_NP;
     // live in-step timing when armed (profiling.h)
     if (arith == ARITH_GENERIC) {
-      SRS_PROBED_LAUNCH(SRS_AMD_PROBE_LDPC_HR, (ldpc_decode_hr_kernel<ARITH_GENERIC, HR_MAXL, HR_NP>), dim3(grid),
-                        dim3(NT), lds, stream, args);
+      SRS_PROBED_LAUNCH(SRS_AMD_PROBE_LDPC_HR, (ldpc_decode_hr_kernel<ARITH_GENERIC, HR_MAXL, 1>), dim3(grid),
+                        dim3(HR_HALF), lds, stream, args);
     } else {
-      SRS_PROBED_LAUNCH(SRS_AMD_PROBE_LDPC_HR, (ldpc_decode_hr_kernel<ARITH_SIMD, HR_MAXL, HR_NP>), dim3(grid),
-                        dim3(NT), lds, stream, args);
+      SRS_PROBED_LAUNCH(SRS_AMD_PROBE_LDPC_HR, (ldpc_decode_hr_kernel<ARITH_SIMD, HR_MAXL, 1>), dim3(grid),
+                        dim3(HR_HALF), lds, stream, args);
     }
     return hipGetLastError();
   }
