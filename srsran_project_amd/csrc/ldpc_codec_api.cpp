@@ -234,17 +234,14 @@ void srs_amd_ldpc_encoder_destroy(srs_amd_ldpc_encoder* encoder)
   destroy_with_stream(encoder);
 }
 
-} // extern "C"
-
-int srs_amd::ldpc_encode_batch_ex(srs_amd_ldpc_encoder*              enc,
+int srs_amd_ldpc_encode_batch(srs_amd_ldpc_encoder*              enc,
                               const srs_amd_ldpc_encoder_config* cfg,
                               const uint8_t*                     d_messages,
                               uint32_t                           msg_stride,
                               uint8_t*                           d_codeblocks,
                               uint32_t                           cb_stride,
                               uint32_t                           nof_cbs,
-                              void*                              stream,
-                              uint32_t                           max_bits)
+                              void*                              stream)
 {
   if (enc == nullptr) {
     return fail(SRS_AMD_EINVAL, "null encoder");
@@ -279,34 +276,14 @@ int srs_amd::ldpc_encode_batch_ex(srs_amd_ldpc_encoder*              enc,
   a.msg_stride = msg_stride;
   a.cw_stride  = cb_stride;
   a.nof_cbs    = nof_cbs;
-  // Rows whose parity columns hold shortened-codeword positions < max_bits (column c at (c - 2) Z).
-  const uint32_t full_bits = static_cast<uint32_t>(g.N_short * Z);
-  max_bits                 = std::min(max_bits, full_bits);
-  const int cols           = static_cast<int>((max_bits + Z - 1) / Z) + 2;
-  a.M_eff                  = std::max(4, std::min(a.M, cols - a.K));
-  a.pack_bits              = max_bits == full_bits ? static_cast<int32_t>(full_bits)
-                                                   : static_cast<int32_t>(std::min(full_bits, (max_bits + 7) / 8 * 8));
+  a.M_eff      = a.M; // every extension row, the whole shortened codeword
+  a.pack_bits  = g.N_short * Z;
   std::lock_guard<std::mutex> lock(enc->mtx);
   hipError_t                  e = hipSetDevice(enc->device);
   if (e == hipSuccess) {
     e = launch_ldpc_encode(a, static_cast<int>(std::min(nof_cbs, ENCODE_GRID_CAP)), static_cast<hipStream_t>(stream));
   }
   return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "ldpc_encode_kernel launch");
-}
-
-extern "C" {
-
-int srs_amd_ldpc_encode_batch(srs_amd_ldpc_encoder*              enc,
-                              const srs_amd_ldpc_encoder_config* cfg,
-                              const uint8_t*                     d_messages,
-                              uint32_t                           msg_stride,
-                              uint8_t*                           d_codeblocks,
-                              uint32_t                           cb_stride,
-                              uint32_t                           nof_cbs,
-                              void*                              stream)
-{
-  return ldpc_encode_batch_ex(enc, cfg, d_messages, msg_stride, d_codeblocks, cb_stride, nof_cbs, stream,
-                              0xffffffffu);
 }
 
 int srs_amd_ldpc_encode(srs_amd_ldpc_encoder*              enc,
@@ -416,7 +393,7 @@ int srs_amd_ldpc_rate_match_batch(srs_amd_ldpc_rate_matcher*        rm,
   std::lock_guard<std::mutex> lock(rm->mtx);
   hipError_t                  e = hipSetDevice(rm->device);
   if (e == hipSuccess) {
-    e = launch_rate_match(a, max_rm_length, static_cast<hipStream_t>(stream));
+    e = launch_rate_match(a, static_cast<hipStream_t>(stream));
   }
   return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "ldpc_rate_match_kernel launch");
 }
@@ -602,100 +579,19 @@ const mixed_row_base& mixed_row_of(uint32_t bg, uint32_t Z)
 }
 } // namespace
 
-uint32_t srs_amd::ldpc_encode_mixed_row(void* row, uint32_t bg, uint32_t Z, uint32_t max_bits)
+void srs_amd::ldpc_encode_row_desc(void* row, uint32_t bg, uint32_t Z, uint32_t max_bits)
 {
   // callers pass a validated plan's (bg, Z)
   const mixed_row_base& m = mixed_row_of(bg, Z);
-  // as ldpc_encode_batch_ex: rows whose parity columns hold shortened-codeword positions < max_bits
+  // rows whose parity columns hold shortened-codeword positions < max_bits (column c at (c - 2) Z)
   const uint32_t full_bits = static_cast<uint32_t>(m.N_short) * Z;
   max_bits                 = std::min(max_bits, full_bits);
   const int    cols        = static_cast<int>((max_bits + Z - 1) / Z) + 2;
   enc_row_desc r           = m.r;
   r.M_eff                  = static_cast<uint32_t>(std::max(4, std::min(m.M, cols - m.K)));
   r.pack_bits              = max_bits == full_bits ? full_bits : std::min(full_bits, (max_bits + 7) / 8 * 8);
-  static_assert(sizeof(r) == LDPC_ENCODE_ROW_BYTES, "row descriptor size");
+  static_assert(sizeof(r) == 32, "row descriptor size");
   std::memcpy(row, &r, sizeof(r));
-  return r.M_eff;
-}
-
-int srs_amd::ldpc_encode_mixed(srs_amd_ldpc_encoder* enc,
-                               uint32_t              bg,
-                               uint32_t              max_z,
-                               uint32_t              max_rows_eff,
-                               const uint8_t*        d_messages,
-                               uint32_t              msg_stride,
-                               uint8_t*              d_codeblocks,
-                               uint32_t              cb_stride,
-                               uint32_t              nof_cbs,
-                               void*                 stream,
-                               const void*           d_rows)
-{
-  if (enc == nullptr) {
-    return fail(SRS_AMD_EINVAL, "null encoder");
-  }
-  if (nof_cbs == 0) {
-    return SRS_AMD_OK;
-  }
-  lifted_graph g{};
-  if ((bg != 1 && bg != 2) || !build_lifted_graph(g, static_cast<int>(bg), static_cast<int>(max_z)) || max_z < 32 ||
-      d_messages == nullptr || d_codeblocks == nullptr || d_rows == nullptr) {
-    return fail(SRS_AMD_EINVAL, "invalid mixed-Z encoding (bg %u, max Z %u)", bg, max_z);
-  }
-  encode_args a{};
-  (void)build_encode_params(a, g);
-  a.msgs       = d_messages;
-  a.cws        = d_codeblocks;
-  a.edges      = enc->edges;
-  a.msg_stride = msg_stride;
-  a.cw_stride  = cb_stride;
-  a.nof_cbs    = nof_cbs;
-  a.M_eff      = static_cast<int32_t>(max_rows_eff);
-  a.rows       = static_cast<const enc_row_desc*>(d_rows);
-  std::lock_guard<std::mutex> lock(enc->mtx);
-  hipError_t                  e = hipSetDevice(enc->device);
-  if (e == hipSuccess) {
-    e = launch_ldpc_encode(a, static_cast<int>(std::min(nof_cbs, ENCODE_GRID_CAP)), static_cast<hipStream_t>(stream));
-  }
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "ldpc_encode_kernel launch");
-}
-
-int srs_amd::rate_match_ragged(srs_amd_ldpc_rate_matcher* rm,
-                               const uint8_t*             d_codeblocks,
-                               uint32_t                   cb_stride,
-                               const uint32_t*            d_rm_lengths,
-                               const uint32_t*            d_out_offsets,
-                               const uint32_t*            d_row_geo,
-                               const void*                d_geos,
-                               uint8_t*                   d_output,
-                               uint32_t                   nof_cbs,
-                               void*                      stream)
-{
-  if (rm == nullptr) {
-    return fail(SRS_AMD_EINVAL, "null rate matcher");
-  }
-  if (nof_cbs == 0) {
-    return SRS_AMD_OK;
-  }
-  if (d_codeblocks == nullptr || d_rm_lengths == nullptr || d_out_offsets == nullptr || d_row_geo == nullptr ||
-      d_geos == nullptr || d_output == nullptr) {
-    return fail(SRS_AMD_EINVAL, "null device buffer");
-  }
-  // the caller (srs_amd_pdsch_encode_slot) checked every geometry and cb_stride
-  rate_match_args a{};
-  a.cw          = d_codeblocks;
-  a.cw_stride   = cb_stride;
-  a.rm_lengths  = d_rm_lengths;
-  a.out_offsets = d_out_offsets;
-  a.out         = d_output;
-  a.nof_cbs     = nof_cbs;
-  a.row_geo     = d_row_geo;
-  a.geos        = static_cast<const rm_geometry*>(d_geos);
-  std::lock_guard<std::mutex> lock(rm->mtx);
-  hipError_t                  e = hipSetDevice(rm->device);
-  if (e == hipSuccess) {
-    e = launch_rate_match(a, 0, static_cast<hipStream_t>(stream));
-  }
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "ldpc_rate_match_kernel launch");
 }
 
 int srs_amd::rate_dematch_ragged(srs_amd_ldpc_rate_dematcher* dm,

@@ -27,12 +27,10 @@ struct encode_args {
   int32_t         p0_shift;  // s: p0 = P^-s (sum of lambdas)
   int32_t         core_a[4]; // shift of column K_bg in rows 0..3 (0 where absent)
   int32_t         row_start[MAX_BG_M + 1];
-  // optional per-codeblock lifting size (bit-sliced kernel, every Z >= 32 of one base graph): codeblock cb
-  // uses rows[cb] and its edges at edges + rows[cb].edge_off; Z / M_eff above are then the launch maxima
-  const struct enc_row_desc* rows;
 };
 
-// Per-codeblock graph of a mixed-lifting-size encoder launch (srs_amd_pdsch_encode_slot).
+// Per-codeblock graph and encoded window of the PDSCH codeblock kernel (pdsch_encoder.hip; built by
+// ldpc_encode_row_desc): its edges are at edges + edge_off of the table of every lifted graph.
 struct enc_row_desc {
   uint32_t Z;
   uint32_t edge_off;
@@ -69,15 +67,11 @@ struct rate_match_args {
   uint8_t*        out;
   uint32_t        nof_cbs;
   rm_geometry     g;
-  // optional per-codeblock geometry (replaces g): codeblock cb uses geos[row_geo[cb]]; the codeblocks
-  // of one codeword share a geometry and the codewords of different geometries share no byte
-  const uint32_t*    row_geo;
-  const rm_geometry* geos;
 };
 
 hipError_t launch_ldpc_encode(const encode_args& a, int grid, hipStream_t stream);
 size_t     ldpc_encode_lds_bytes(int K, int M_eff, int Z);
 hipError_t launch_rate_dematch(const dematch_args& a, hipStream_t stream);
-hipError_t launch_rate_match(const rate_match_args& a, uint32_t max_rm_length, hipStream_t stream);
+hipError_t launch_rate_match(const rate_match_args& a, hipStream_t stream);
 
 } // namespace srs_amd

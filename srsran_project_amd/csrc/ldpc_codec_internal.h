@@ -26,20 +26,6 @@ int rate_dematch_batch_ex(srs_amd_ldpc_rate_dematcher*      dm,
                           bool                              fresh,
                           uint32_t                          write_end = 0);
 
-// srs_amd_ldpc_encode_batch producing only the first max_bits of each shortened
-// codeword (the rows of the extension region beyond them are not computed and
-// the codeblock rows are written up to ceil(max_bits / 8) bytes): what a rate
-// matcher reading the circular buffer window [0, max_bits) needs.
-int ldpc_encode_batch_ex(srs_amd_ldpc_encoder*              enc,
-                         const srs_amd_ldpc_encoder_config* cfg,
-                         const uint8_t*                     d_messages,
-                         uint32_t                           msg_stride,
-                         uint8_t*                           d_codeblocks,
-                         uint32_t                           cb_stride,
-                         uint32_t                           nof_cbs,
-                         void*                              stream,
-                         uint32_t                           max_bits);
-
 // srs_amd_ldpc_decode_batch with an optional per-codeblock skip flag (int32 at d_skip_flags + cb *
 // skip_stride, non-zero: not decoded, nof_iters[cb] = -2): the PUSCH decoder's retransmissions of
 // codeblocks whose CRC passed in an earlier transmission (pusch_decoder_impl.cpp:330-345).
@@ -91,41 +77,13 @@ int ldpc_decode_mixed(srs_amd_ldpc_decoder* d,
 // Device row descriptor of ldpc_decode_mixed (16 bytes) for a codeblock of lifting size Z and CRC poly.
 void ldpc_mixed_row(void* row, uint32_t bg, uint32_t Z, int crc_poly);
 
-// LDPC encoding of codeblocks of one base graph with per-codeblock lifting sizes (all >= 32) in one launch
-// (srs_amd_pdsch_encode_slot): d_rows holds ldpc_encode_mixed_row descriptors; max_z / max_rows_eff size the
-// launch (the largest Z and extension row count of the batch).
-int ldpc_encode_mixed(srs_amd_ldpc_encoder* enc,
-                      uint32_t              bg,
-                      uint32_t              max_z,
-                      uint32_t              max_rows_eff,
-                      const uint8_t*        d_messages,
-                      uint32_t              msg_stride,
-                      uint8_t*              d_codeblocks,
-                      uint32_t              cb_stride,
-                      uint32_t              nof_cbs,
-                      void*                 stream,
-                      const void*           d_rows);
+// Encoder row descriptor (enc_row_desc, 32 bytes, written to row) the PDSCH codeblock kernel reads for a codeblock
+// of base graph bg and lifting size Z whose rate matcher reads the first max_bits of the shortened codeword: the
+// extension rows beyond them are not computed.
+void ldpc_encode_row_desc(void* row, uint32_t bg, uint32_t Z, uint32_t max_bits);
 
-// Row descriptor (32 bytes) of ldpc_encode_mixed for a codeblock of lifting size Z whose rate matcher reads
-// the first max_bits of the shortened codeword; returns the extension rows it computes (M_eff).
-uint32_t ldpc_encode_mixed_row(void* row, uint32_t bg, uint32_t Z, uint32_t max_bits);
-constexpr size_t LDPC_ENCODE_ROW_BYTES = 32;
-
-// Device table of every lifted graph's edges (ldpc_encode_mixed_row's edge_off indexes it).
+// Device table of every lifted graph's edges (enc_row_desc::edge_off indexes it).
 const uint32_t* ldpc_encoder_edges(const srs_amd_ldpc_encoder* enc);
-
-// Rate matching of codeblocks with per-codeblock geometry (srs_amd_pdsch_encode_slot): codeblock cb uses
-// geos[row_geo[cb]]; d_out_offsets are bit offsets into d_output.
-int rate_match_ragged(srs_amd_ldpc_rate_matcher* rm,
-                      const uint8_t*             d_codeblocks,
-                      uint32_t                   cb_stride,
-                      const uint32_t*            d_rm_lengths,
-                      const uint32_t*            d_out_offsets,
-                      const uint32_t*            d_row_geo,
-                      const void*                d_geos,
-                      uint8_t*                   d_output,
-                      uint32_t                   nof_cbs,
-                      void*                      stream);
 
 // Rate dematching of codeblocks with per-codeblock geometry (srs_amd_pusch_decode_slot): codeblock cb
 // uses geos[row_geo[cb]] and writes soft-buffer bytes [0, geo_write_end[row_geo[cb]]) of its row

@@ -420,12 +420,11 @@ __device__ uint32_t rm_byte(const rate_match_args& a, const rm_geometry& g, cons
 // bytes (partial last group, unaligned segments, Qm = 1): one thread per output byte gathering its 8 bits
 // (bit selection + interleaver as index arithmetic); a byte straddling the next segment is built from global
 // memory.
-template <bool RAGGED>
 __global__ __launch_bounds__(RATE_MATCH_THREADS) void ldpc_rate_match_kernel(rate_match_args a)
 {
   __shared__ uint8_t s_cw[RM_MAX_CW_BYTES + 4]; // + the second byte of a two-byte read at the end
   for (uint32_t cb = blockIdx.y; cb < a.nof_cbs; cb += gridDim.y) {
-    const rm_geometry g = RAGGED ? a.geos[a.row_geo[cb]] : a.g;
+    const rm_geometry g = a.g;
     const fast_div    divL(g.L);
     const uint32_t    cw_bytes = (g.Ncb + 7) / 8;
     const uint32_t off   = a.out_offsets[cb];
@@ -532,16 +531,11 @@ hipError_t launch_rate_dematch(const dematch_args& a, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_rate_match(const rate_match_args& a, uint32_t max_rm_length, hipStream_t stream)
+hipError_t launch_rate_match(const rate_match_args& a, hipStream_t stream)
 {
   // one workgroup per codeblock: the staged circular buffer is loaded once
-  (void)max_rm_length;
   dim3 grid(1, a.nof_cbs < 65535u ? a.nof_cbs : 65535u);
-  if (a.row_geo != nullptr) {
-    hipLaunchKernelGGL(ldpc_rate_match_kernel<true>, grid, dim3(RATE_MATCH_THREADS), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(ldpc_rate_match_kernel<false>, grid, dim3(RATE_MATCH_THREADS), 0, stream, a);
-  }
+  hipLaunchKernelGGL(ldpc_rate_match_kernel, grid, dim3(RATE_MATCH_THREADS), 0, stream, a);
   return hipGetLastError();
 }
 

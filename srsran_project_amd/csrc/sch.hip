@@ -1,7 +1,5 @@
-// sch.hip -- transport-block kernels of the PDSCH encoder and PUSCH decoder.
+// sch.hip -- transport-block kernels of the PUSCH decoder (the PDSCH encoder's are in pdsch_encoder.hip).
 //
-//   segment_kernel   TX segmentation (ldpc_segmenter_tx_impl.cpp:137-207): one
-//                    thread per output byte of a (TB, segment) message row.
 //   asm_copy_kernel  HARQ message copies into the soft buffer, one thread per
 //                    4 message bytes of the batch;
 //   assemble_kernel  RX tail of pusch_decoder_impl.cpp:309-500: one workgroup per
@@ -11,14 +9,16 @@
 //                    and the TB CRC24A computed from the concatenated bytes as
 //                    they are produced, 2 KiB of a TB per workgroup (linear
 //                    CRC, crc_device.h, partials XOR-ed with atomics);
-//   asm_final_kernel the TB CRC verdict and the HARQ flag reset.
-// Heterogeneous slots (srs_amd_pdsch_encode_slot / srs_amd_pusch_decode_slot) read per-TB descriptors
-// (tb_desc): the assembly kernels above through view_of(), and the TX kernels
-//   tx_tb_crc_kernel  TB CRC16 / CRC24A per TB, 8 KiB of a TB per workgroup, partials XOR-ed per TB;
-//   tx_segment_kernel segmentation with per-TB geometry, one thread per message byte;
-//   tx_cb_crc_kernel  CRC24B attachment of the codeblocks of segmented TBs, one wave per codeblock.
-// Both are byte-gather kernels far below any roofline next to the LDPC
-// kernels they sit between (a few hundred KB per slot).
+//   asm_final_kernel the TB CRC verdict and the HARQ flag reset;
+//   asm_merged_kernel assemble_kernel and asm_tb_kernel in one launch when no HARQ state is kept.
+// Heterogeneous slots (srs_amd_pusch_decode_slot) read per-TB descriptors (tb_desc) through view_of(); their HARQ
+// state moves through
+//   harq_gather_kernel / harq_scatter_kernel / harq_final_kernel  soft bits, messages and CRC flags between the
+//                    callers' soft buffers and the decoder rows (sch_args.h harq_args);
+//   slot_row_patch_kernel  rows of a UE whose UL-SCH geometry is selected on the device.
+// rm_arrays_kernel writes the rate-(de)matching lengths and offsets of a uniform batch.
+// All are byte-gather kernels far below any roofline next to the LDPC kernels they follow (a few hundred KB per
+// slot).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -29,7 +29,6 @@
 namespace srs_amd {
 namespace {
 
-constexpr int SEG_THREADS = 256;
 constexpr int ASM_THREADS = 256;
 constexpr uint32_t CRC24A_POLY = 0x1864cfb;
 constexpr uint32_t SCH_MAX_SEGMENTS = 512;
@@ -39,203 +38,6 @@ constexpr uint32_t ASM_TB_CHUNK     = ASM_THREADS * ASM_TB_PER;  // TB bytes per
 __device__ __forceinline__ uint32_t bit_at(const uint8_t* b, uint32_t p)
 {
   return (b[p >> 3] >> (7 - (p & 7))) & 1u;
-}
-
-// Byte j of segment message row: n_data TB bits from bit tb_off, then (last segment) the TB CRC, zeros after.
-__device__ __forceinline__ uint8_t segment_byte(const uint8_t* tb, uint32_t tb_off, uint32_t n_data, bool last,
-                                                uint32_t crc, uint32_t tb_crc_bits, uint32_t j)
-{
-  if (8 * j + 8 <= n_data) {
-    // all 8 bits from the TB: one or two byte loads
-    const uint32_t q  = tb_off + 8 * j;
-    const uint32_t sh = q & 7u;
-    uint32_t       w  = static_cast<uint32_t>(tb[q >> 3]) << 8;
-    if (sh != 0) {
-      w |= tb[(q >> 3) + 1];
-    }
-    return static_cast<uint8_t>(w >> (8 - sh));
-  }
-  uint32_t byte = 0;
-  for (int k = 0; k < 8; ++k) {
-    const uint32_t p = 8 * j + k;
-    uint32_t       v = 0;
-    if (p < n_data) {
-      v = bit_at(tb, tb_off + p);
-    } else if (last && p < n_data + tb_crc_bits) {
-      v = (crc >> (tb_crc_bits - 1 - (p - n_data))) & 1u;
-    }
-    byte |= v << (7 - k);
-  }
-  return static_cast<uint8_t>(byte);
-}
-
-__global__ __launch_bounds__(SEG_THREADS) void segment_kernel(segment_args a)
-{
-  const uint32_t row = blockIdx.y;
-  const uint32_t j   = blockIdx.x * SEG_THREADS + threadIdx.x;
-  if (row >= a.nof_rows || j >= a.msg_bytes) {
-    return;
-  }
-  const uint32_t t      = row / a.nof_segments;
-  const uint32_t r      = row - t * a.nof_segments;
-  const bool     last   = r == a.nof_segments - 1;
-  const uint32_t n_data = last ? a.last_data_bits : a.cb_info_bits;
-  const uint8_t* tb     = a.tbs + static_cast<size_t>(t) * a.tb_stride;
-  a.msgs[static_cast<size_t>(row) * a.msg_stride + j] =
-      segment_byte(tb, r * a.cb_info_bits, n_data, last, a.tb_crcs[t], a.tb_crc_bits, j);
-}
-
-// Segmentation and CRC24B attachment in one pass (C > 1): one wave per (TB, segment) row.  Lane l builds
-// the contiguous message bytes [l per, (l + 1) per) in registers (segment_byte), divides them into its CRC
-// contribution, the wave XOR-reduces the codeblock CRC, every lane patches the CRC bits that fall into its
-// own bytes and stores them: the message row is written once and never read back.
-constexpr int      SEGCRC_THREADS = 64;
-constexpr uint32_t SEGCRC_PER     = 20; // bytes per lane: 64 x 20 >= 1,056 (BG1 K = 8,448 bits)
-
-__global__ __launch_bounds__(SEGCRC_THREADS) void segment_crc_kernel(segment_args a)
-{
-  __shared__ uint32_t T[256];
-  // the segment's TB bytes (coalesced loads), then the message row (coalesced stores)
-  __shared__ __attribute__((aligned(16))) uint8_t s_io[SEGCRC_THREADS * SEGCRC_PER + 8];
-  crc_table8_init<SEGCRC_THREADS>(T, 24, a.cb_crc_poly);
-  const uint32_t row = blockIdx.x;
-  const uint32_t t   = row / a.nof_segments;
-  const uint32_t r   = row - t * a.nof_segments;
-  const bool     last   = r == a.nof_segments - 1;
-  const uint32_t n_data = last ? a.last_data_bits : a.cb_info_bits;
-  const uint8_t* tb     = a.tbs + static_cast<size_t>(t) * a.tb_stride;
-  const uint32_t crc_t  = a.tb_crcs[t];
-  const uint32_t b0     = threadIdx.x * SEGCRC_PER;
-  const uint32_t off    = r * a.cb_info_bits;        // first TB bit of the segment
-  const uint32_t q0     = off >> 3;                   // its byte
-  const uint32_t nsrc   = (off + n_data + 7) / 8 - q0; // TB bytes the segment touches (<= msg_bytes + 1)
-  for (uint32_t i = threadIdx.x; i < nsrc; i += SEGCRC_THREADS) {
-    s_io[i] = tb[q0 + i];
-  }
-  __syncthreads(); // T, s_io ready
-  uint32_t v[SEGCRC_PER];
-#pragma unroll
-  for (uint32_t k = 0; k < SEGCRC_PER; ++k) {
-    const uint32_t j = b0 + k;
-    v[k]             = j < a.msg_bytes ? segment_byte(s_io, off & 7u, n_data, last, crc_t, a.tb_crc_bits, j) : 0u;
-  }
-  // CRC contribution of this lane's bits below n = cb_info_bits, moved to n (crc_device.h)
-  const uint32_t n    = a.cb_info_bits;
-  const uint32_t full = n / 8;
-  uint32_t       rem  = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < SEGCRC_PER; ++k) {
-    const uint32_t j = b0 + k;
-    if (j < full) {
-      rem = T[rem >> 16] ^ ((rem << 8) & 0xffffffu) ^ v[k];
-    } else if (j == full && (n & 7u) != 0) {
-      for (uint32_t i = 0; i < (n & 7u); ++i) {
-        rem = (rem << 1) | ((v[k] >> (7 - i)) & 1u);
-        if (rem & 0x1000000u) {
-          rem ^= a.cb_crc_poly;
-        }
-      }
-    }
-  }
-  uint32_t contrib = 0;
-  if (b0 * 8 < n) {
-    const uint32_t e = min(n, (b0 + SEGCRC_PER) * 8);
-#pragma unroll
-    for (uint32_t i = 0; i < 24; ++i) {
-      contrib ^= a.cb_crc_table[n - e + i] & (0u - ((rem >> i) & 1u));
-    }
-  }
-  const uint32_t crc = crc_wave_xor(contrib);
-  __syncthreads(); // every lane has read its TB bytes from s_io
-#pragma unroll
-  for (uint32_t k = 0; k < SEGCRC_PER; ++k) {
-    s_io[b0 + k] = static_cast<uint8_t>(v[k]);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    attach_crc_bits(s_io, n, 24, crc); // the CRC bits [n, n + 24): at most four LDS bytes
-  }
-  __syncthreads();
-  uint8_t* m = a.msgs + static_cast<size_t>(row) * a.msg_stride;
-  if ((reinterpret_cast<uintptr_t>(m) & 3u) == 0) {
-    for (uint32_t w = threadIdx.x; w < (a.msg_bytes + 3) / 4; w += SEGCRC_THREADS) {
-      reinterpret_cast<uint32_t*>(m)[w] = reinterpret_cast<const uint32_t*>(s_io)[w]; // row padded to 64 B
-    }
-  } else {
-    for (uint32_t i = threadIdx.x; i < a.msg_bytes; i += SEGCRC_THREADS) {
-      m[i] = s_io[i];
-    }
-  }
-}
-
-// ---- PDSCH encoder of a heterogeneous batch (srs_amd_pdsch_encode_slot) ----
-
-// TB CRC (CRC16 / CRC24A per TB): one workgroup per ASM_TB_CHUNK bytes of a TB, partials XOR-ed into acc[t].
-__global__ __launch_bounds__(ASM_THREADS) void tx_tb_crc_kernel(tx_slot_args a)
-{
-  __shared__ uint32_t partial[ASM_THREADS / 64];
-  __shared__ uint32_t T[256];
-  const uint32_t      t      = blockIdx.y;
-  const tb_desc       d      = a.tds[t];
-  const uint32_t      nbytes = d.tbs_bits / 8;
-  const uint32_t      c0     = blockIdx.x * ASM_TB_CHUNK;
-  if (c0 >= nbytes) {
-    return; // uniform over the workgroup
-  }
-  const bool      c16   = d.tb_crc_bits == 16;
-  const uint32_t  poly  = c16 ? a.crc16_poly : a.crc24a_poly;
-  const uint32_t* table = c16 ? a.crc16_table : a.crc24a_table;
-  __shared__ __attribute__((aligned(16))) uint8_t s_chunk[ASM_TB_CHUNK];
-  crc_table8_init<ASM_THREADS>(T, d.tb_crc_bits, poly);
-  crc_stage_bytes<ASM_THREADS>(s_chunk, a.tbs + d.tb_offset, c0, min(ASM_TB_CHUNK, nbytes - c0)); // coalesced
-  __syncthreads();
-  const uint32_t b0 = c0 + threadIdx.x * ASM_TB_PER;
-  const uint32_t b1 = min(nbytes, b0 + ASM_TB_PER);
-  const uint32_t to = min(d.tbs_bits, (c0 + ASM_TB_CHUNK) * 8); // moved to the TB end once per workgroup
-  const uint32_t x  = crc_block_xor<ASM_THREADS>(
-      crc_chunk_contrib(lds_chunk_fetch{s_chunk, c0}, b0, b1, d.tbs_bits, d.tb_crc_bits, poly, table, T, to),
-      partial);
-  if (threadIdx.x == 0 && x != 0) {
-    atomicXor(a.acc + t, crc_move(x, d.tbs_bits - to, d.tb_crc_bits, table));
-  }
-}
-
-// Segmentation (ldpc_segmenter_tx_impl.cpp:137-207) with per-TB geometry: one thread per message byte.
-__global__ __launch_bounds__(SEG_THREADS) void tx_segment_kernel(tx_slot_args a)
-{
-  const uint32_t row = blockIdx.y;
-  const uint32_t j   = blockIdx.x * SEG_THREADS + threadIdx.x;
-  const uint32_t t   = a.row_tb[row];
-  const tb_desc  d   = a.tds[t];
-  if (j >= d.msg_bytes) {
-    return;
-  }
-  const uint32_t r      = row - d.row0;
-  const bool     last   = r == d.nof_segments - 1;
-  const uint32_t n_data = last ? d.cb_info_bits - d.tb_crc_bits - d.zero_pad : d.cb_info_bits;
-  a.msgs[static_cast<size_t>(row) * a.msg_stride + j] =
-      segment_byte(a.tbs + d.tb_offset, r * d.cb_info_bits, n_data, last, a.acc[t], d.tb_crc_bits, j);
-}
-
-// CRC24B attachment to the codeblocks of segmented TBs (ldpc_segmenter_tx_impl.cpp:196): one wave per row,
-// the CRC bits MSB-first into message bits [cb_info_bits, cb_info_bits + 24).
-__global__ __launch_bounds__(64) void tx_cb_crc_kernel(tx_slot_args a)
-{
-  __shared__ uint32_t partial[1];
-  __shared__ uint32_t T[256];
-  const uint32_t      row = blockIdx.x;
-  const tb_desc       d   = a.tds[a.row_tb[row]];
-  if (d.nof_segments == 1) {
-    return;
-  }
-  crc_table8_init<64>(T, 24, a.crc24b_poly);
-  __syncthreads();
-  uint8_t*       m   = a.msgs + static_cast<size_t>(row) * a.msg_stride;
-  const uint32_t n   = d.cb_info_bits;
-  const uint32_t crc = block_crc_bytes<64>(row_fetch{m}, n, 24, a.crc24b_poly, a.crc24b_table, T, partial);
-  if (threadIdx.x == 0) {
-    attach_crc_bits(m, n, 24, crc);
-  }
 }
 
 // TB byte j (bits 8j..8j+7) gathered from the concatenated codeblock data bits.
@@ -480,7 +282,11 @@ __device__ __forceinline__ void asm_tb_chunk(const assemble_args& a, uint32_t t,
       return;
     }
   }
-  crc_table8_init<ASM_THREADS>(T, 24, CRC24A_POLY);
+  // The order and polynomial of crc_table8_init, and the order of crc_move below, are constants the optimiser sees
+  // only after it has inlined the two helpers (readfirstlane of a constant folds to it then).  Given the literals, it
+  // specialises the helpers before inlining them, this being their only caller in the file, and the table build
+  // becomes eight one-bit steps instead of four two-bit ones.
+  crc_table8_init<ASM_THREADS>(T, __builtin_amdgcn_readfirstlane(24u), __builtin_amdgcn_readfirstlane(CRC24A_POLY));
   uint32_t        stride;
   const uint8_t*  src    = asm_source(a, v, stride);
   const tb_gather g{src, stride, v.cbi};
@@ -512,7 +318,7 @@ __device__ __forceinline__ void asm_tb_chunk(const assemble_args& a, uint32_t t,
       crc_chunk_contrib(lds_fetch{s_chunk, c0}, b0, b1, v.tbs_bits, 24, CRC24A_POLY, a.crc24a_table, T, to),
       partial);
   if (threadIdx.x == 0 && x != 0) {
-    atomicXor(a.acc + t, crc_move(x, v.tbs_bits - to, 24, a.crc24a_table));
+    atomicXor(a.acc + t, crc_move(x, v.tbs_bits - to, __builtin_amdgcn_readfirstlane(24u), a.crc24a_table));
   }
 }
 
@@ -746,42 +552,6 @@ hipError_t launch_rm_arrays(uint32_t* arrays, uint32_t nof_tbs, uint32_t C, uint
   const uint32_t rows = nof_tbs * C;
   hipLaunchKernelGGL(rm_arrays_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, arrays, rows, C, nof_short,
                      e_short, e_long, tb_units);
-  return hipGetLastError();
-}
-
-bool segment_attaches_crc(const segment_args& a)
-{
-  return a.cb_crc_table != nullptr && a.msg_bytes <= SEGCRC_THREADS * SEGCRC_PER;
-}
-
-hipError_t launch_segment(const segment_args& a, hipStream_t stream)
-{
-  if (a.nof_rows == 0) {
-    return hipSuccess;
-  }
-  if (segment_attaches_crc(a)) {
-    hipLaunchKernelGGL(segment_crc_kernel, dim3(a.nof_rows), dim3(SEGCRC_THREADS), 0, stream, a);
-    return hipGetLastError();
-  }
-  dim3 grid((a.msg_bytes + SEG_THREADS - 1) / SEG_THREADS, a.nof_rows);
-  hipLaunchKernelGGL(segment_kernel, grid, dim3(SEG_THREADS), 0, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_tx_slot_segment(const tx_slot_args& a, hipStream_t stream)
-{
-  if (a.nof_tbs == 0) {
-    return hipSuccess;
-  }
-  hipError_t e = hipMemsetAsync(a.acc, 0, sizeof(uint32_t) * a.nof_tbs, stream);
-  if (e != hipSuccess) {
-    return e;
-  }
-  hipLaunchKernelGGL(tx_tb_crc_kernel, dim3((a.max_tb_bytes + ASM_TB_CHUNK - 1) / ASM_TB_CHUNK, a.nof_tbs),
-                     dim3(ASM_THREADS), 0, stream, a);
-  hipLaunchKernelGGL(tx_segment_kernel, dim3((a.max_msg_bytes + SEG_THREADS - 1) / SEG_THREADS, a.nof_rows),
-                     dim3(SEG_THREADS), 0, stream, a);
-  hipLaunchKernelGGL(tx_cb_crc_kernel, dim3(a.nof_rows), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -13,27 +13,6 @@ namespace srs_amd {
 struct rm_geometry;
 struct enc_row_desc;
 
-// ldpc_segmenter_tx_impl::read_codeblock (ldpc_segmenter_tx_impl.cpp:137-207) for
-// every (TB, segment) pair: data bits, TB CRC + zero pad in the last segment,
-// zeros where the CB CRC (attached afterwards) and the filler bits go.
-struct segment_args {
-  const uint8_t*  tbs;        // nof_tbs rows of tb_stride bytes
-  const uint32_t* tb_crcs;    // TB checksum per TB
-  uint8_t*        msgs;       // nof_tbs * C rows of msg_stride bytes
-  uint32_t        tb_stride;
-  uint32_t        msg_stride;
-  uint32_t        msg_bytes;  // ceil(K / 8)
-  uint32_t        nof_segments;
-  uint32_t        cb_info_bits;
-  uint32_t        last_data_bits; // TB bits in the last segment
-  uint32_t        tb_crc_bits;
-  uint32_t        nof_rows;   // nof_tbs * C
-  // CRC24B attachment in the same pass (C > 1): the codeblock CRC over bits [0, cb_info_bits) written at
-  // bit cb_info_bits (ldpc_segmenter_tx_impl.cpp:196); null table: segmentation only
-  const uint32_t* cb_crc_table; // x^(k+24) mod g (crc_linear_table)
-  uint32_t        cb_crc_poly;
-};
-
 // Per-CB soft-buffer row (HARQ rx_buffer): [soft LLRs | saved message | CRC flag].
 struct soft_row_layout {
   uint32_t soft_bytes; // N_short * Z
@@ -55,26 +34,6 @@ struct tb_desc {
   uint32_t msg_bytes;   // ceil(K / 8)
   uint32_t pad;         // decode: index of the TB's first codeblock in assemble_args::cb_iterations
 };
-
-// PDSCH encoder of a heterogeneous batch: TB CRCs (CRC16 or CRC24A per TB, linear CRC over chunks XOR-ed
-// into acc[t]), segmentation, and the CRC24B of the codeblocks of segmented TBs (per-row lengths).
-struct tx_slot_args {
-  const uint8_t*  tbs;        // TB bytes (tds[t].tb_offset)
-  const tb_desc*  tds;
-  const uint32_t* row_tb;     // TB of each message row
-  uint32_t*       acc;        // per-TB CRC accumulators (zeroed before tx_tb_crc_kernel)
-  uint8_t*        msgs;       // message rows of msg_stride bytes
-  const uint32_t* crc16_table;
-  const uint32_t* crc24a_table;
-  const uint32_t* crc24b_table;
-  uint32_t        crc16_poly, crc24a_poly, crc24b_poly;
-  uint32_t        msg_stride;
-  uint32_t        nof_tbs;
-  uint32_t        nof_rows;
-  uint32_t        max_tb_bytes;
-  uint32_t        max_msg_bytes;
-};
-hipError_t launch_tx_slot_segment(const tx_slot_args& a, hipStream_t stream);
 
 // Fused PDSCH encoder (pdsch_encoder.hip): one workgroup per codeblock that builds, CRC-attaches, LDPC-encodes and
 // rate-matches its codeblock in LDS; the TB CRC is gathered from per-codeblock partials by the TB's last codeblock.
@@ -197,9 +156,6 @@ struct slot_row_patch {
 };
 hipError_t launch_slot_row_patch(const slot_row_patch* items, uint32_t n, hipStream_t stream);
 
-hipError_t launch_segment(const segment_args& a, hipStream_t stream);
-// true when launch_segment also attaches the codeblock CRCs (segment_crc_kernel)
-bool       segment_attaches_crc(const segment_args& a);
 // Per-codeblock rate-matching lengths and codeword offsets of nof_tbs transport blocks of one plan
 // (srs_amd_sch_plan_segments per TB), written on the device: arrays[row] = E_r, arrays[rows + row] =
 // tb * tb_units + offset_r, row = tb * C + r.  No host upload, so a plan change never blocks the host.

@@ -1,6 +1,6 @@
 """Host time of each C-ABI call of one slot_pipeline step (perf_counter around the call: descriptor building,
-uploads and any host wait inside it) next to the step's wall time, with the packed decoder and the fused PDSCH
-encoder switched on and off in-process (both read their environment switch per call).
+uploads and any host wait inside it) next to the step's wall time, with the packed decoder switched on and off
+in-process (it reads its environment switch per call).
   PYTHONPATH=. python tools/slot_host_probe.py [cells]"""
 import os
 import sys
@@ -46,10 +46,8 @@ def step():
     stream.wait_event(pl.ev_join)
 
 
-for cfg in [{}, {"SRSRAN_AMD_LDPC_PK": "0"}, {"SRSRAN_AMD_PDSCH_FUSED": "0"},
-            {"SRSRAN_AMD_LDPC_PK": "0", "SRSRAN_AMD_PDSCH_FUSED": "0"}]:
-    for k in ("SRSRAN_AMD_LDPC_PK", "SRSRAN_AMD_PDSCH_FUSED"):
-        os.environ.pop(k, None)
+for cfg in [{}, {"SRSRAN_AMD_LDPC_PK": "0"}]:
+    os.environ.pop("SRSRAN_AMD_LDPC_PK", None)
     os.environ.update(cfg)
     for _ in range(3):
         step()
