@@ -838,7 +838,10 @@ __global__ __launch_bounds__(ST) void chest_stats_kernel(chest_args a_in, chest_
     const float rsrp   = rsrp_sum / (npilt * static_cast<float>(a.L));
     const float epre   = tot.z / npilt;
     float       nvar   = nsum / (npilt * static_cast<float>(a.ncdm) - 1.0f);
-    nvar               = fmaxf(rsrp / 1e10f, nvar);
+    // std::max(floor, nvar) as the reference writes it (:160-161): a NaN floor (a non-finite RSRP) is kept, where
+    // fmaxf would drop it for the finite nvar and report a noise variance of 0 next to a NaN RSRP
+    const float nfloor = rsrp / 1e10f;
+    nvar               = nfloor < nvar ? nvar : nfloor;
     const float datarp = rsrp * static_cast<float>(a.L) / a.beta / a.beta;
     const float snr    = isnormal(nvar) ? datarp / nvar : 0.0f;
 

@@ -397,6 +397,45 @@ def test_pusch_chest_matches_reference(case):
     chest_cases.assert_stats_close(gs, ws, case[0])
 
 
+@pytest.mark.parametrize("case", chest_cases.EDGE_CASES, ids=chest_cases.EDGE_IDS)
+def test_pusch_chest_coherent_matches_reference(case):
+    """The oracle on grids that hold the DM-RS (chest_cases.coherent_grid) at the estimator's edges, and -- on the
+    reference's own results -- that each case is what its name says: the injected delay recovered within one tap
+    of the time-alignment IDFT with its sign (outside the half-CP window: not recovered), the injected CFO within
+    5 % + 2 Hz with its sign (one DM-RS symbol: no CFO), an SNR of a usable link."""
+    from oracle import chest
+
+    name, mu, delay, cfo, snr = case[0], case[12], case[14], case[15], case[16]
+    grid, kw, est0, got, gs = chest_cases.edge_args(case)
+    want, ws = chest.ref_pusch_chest(grid, estimates=est0, **kw)
+    chest_cases.assert_estimates_close(got, want, name)
+    chest_cases.assert_stats_close(gs, ws, name)
+    truth = chest_cases.edge_truth(case)
+    nds = bin(kw["symbols_mask"]).count("1")
+    for p, st in enumerate(ws):
+        ta, tap = float(st["time_alignment_s"]), truth["tap_s"]
+        if name == "ta_beyond_window":
+            assert abs(ta) < truth["half_cp_s"] and abs(ta - truth["ta_s"]) > tap, (name, p, ta, truth)
+        elif kw["fd"] == 1:
+            # mean smoothing: the time alignment is taken from the smoothed pilots, all equal, whose IDFT peaks at
+            # tap 0 whatever the delay
+            assert ta == 0.0, (name, p, ta)
+        else:
+            assert abs(ta - truth["ta_s"]) <= tap, (name, p, ta, truth)
+            assert delay == 0 or np.sign(ta) == np.sign(delay), (name, p, ta, delay)
+        c = float(st["cfo_hz"])
+        if nds == 1:
+            assert np.isnan(c), (name, p, c)
+        else:
+            assert abs(c - truth["cfo_hz"]) <= 0.05 * abs(truth["cfo_hz"]) + 2.0, (name, p, c, truth)
+            assert cfo == 0 or np.sign(c) == np.sign(cfo), (name, p, c, cfo)
+        if name not in ("ta_beyond_window", "1dmrs_4l_mean"):
+            assert 10 * np.log10(float(st["snr"])) >= 12.0, (name, p, st["snr"])
+        if snr is None:  # no noise: the SINR ceiling of 100 dB
+            assert np.isclose(float(st["snr"]), 1e10, rtol=1e-5), (name, p, st["snr"])
+            assert np.isclose(float(st["noise_var"]), float(st["rsrp"]) / 1e10, rtol=1e-6), (name, p, st)
+
+
 @pytest.mark.skipif(oracle.REF is None, reason="oracle/_ref not built")
 @pytest.mark.parametrize("case_idx", range(10))
 def test_pusch_demodulator_matches_reference(case_idx):

@@ -79,6 +79,51 @@ def test_pusch_processor_vs_reference(case):
         assert want["tb_crc_ok"] and np.array_equal(got_tb, tb), name
 
 
+def delayed_grid(case, numerology, delay, cfo):
+    """The bwp_part_2rx_16qam-style transmission of `case` received with a timing offset (delay in units of
+    1 / (4096 scs): a linear phase over the subcarriers) and a CFO (cycles per symbol duration: a phase per OFDM
+    symbol at its start epoch), rounded back to bf16.  Returns (pdu, tbs, transport block, grid)."""
+    from oracle import chest
+    from pusch_slot_cases import _bf16, _cplx
+
+    name, over, nprb, ch, snr, _ = case
+    pdu = dict(BASE, **over, numerology=numerology)
+    tbs = _tbs(pdu)
+    pdu["base_graph"] = 2 if (tbs <= 292 or (tbs <= 3824 and pdu["target_code_rate"] / 1024 <= 0.67)
+                              or pdu["target_code_rate"] / 1024 <= 0.25) else 1
+    tb = np.random.default_rng(hash(name) % 1000).integers(0, 256, tbs // 8, dtype=np.uint8)
+    grid, _ = pp.ue_transmit(tb, pdu, 12 * nprb, channel=ch, snr_db=snr, seed=5)
+    z = _cplx(grid)
+    k = np.arange(12 * nprb)
+    epoch = chest.symbol_start_epochs(numerology).astype(np.float64)
+    z = z * np.exp(-2j * np.pi * k * delay / 4096)[None, None, :] * np.exp(2j * np.pi * cfo * epoch)[None, :, None]
+    return pdu, tbs, tb, _bf16(z)
+
+
+@pytest.mark.parametrize("numerology,delay,cfo", [(1, -20.0, 0.003), (1, 35.0, -0.003), (0, 20.0, 0.002)],
+                         ids=["advance_cfo_pos", "delay_cfo_neg", "mu0_delay_cfo_pos"])
+def test_pusch_processor_delay_and_cfo_vs_reference(numerology, delay, cfo):
+    """The estimator feeding the fused equalizer on a transmission that arrives early or late and turns from
+    symbol to symbol (every other end-to-end case has time alignment 0 and CFO 0): TB bytes, CRC, LDPC
+    statistics and CSI as the compiled pusch_processor_impl, whose time alignment has the injected sign."""
+    case = CASES[2]
+    assert case[0] == "bwp_part_2rx_16qam"
+    iters = case[5]
+    pdu, tbs, tb, grid = delayed_grid(case, numerology, delay, cfo)
+    want_tb, want = pp.ref_pusch_process(grid, pdu, tbs // 8, iterations=iters)
+    assert want["time_alignment_s"] != 0 and np.sign(want["time_alignment_s"]) == np.sign(delay), want
+    proc = amd.PuschProcessor(amd.PuschProcessorConfig(dec_nof_iterations=iters), device=0)
+    plan = proc.plan(amd.make_pdu(**dict(pdu, tbs=tbs)), 12 * case[2])
+    got_tb, got = proc.process(grid, plan)
+    assert bool(got.data.tb_crc_ok) == want["tb_crc_ok"]
+    assert np.array_equal(got_tb, want_tb)
+    assert got.data.nof_codeblocks_total == want["nof_codeblocks_total"]
+    assert got.data.ldpc_iterations_sum == want["iterations_sum"], (got.data.ldpc_iterations_sum, want)
+    assert got.data.ldpc_iterations_max == want["iterations_max"]
+    _check_csi(got, want, "delay %g cfo %g" % (delay, cfo))
+    assert want["tb_crc_ok"] and np.array_equal(got_tb, tb)
+
+
 def test_pusch_processor_harq_combining():
     """rv 0 at an SNR where the TB fails, then rv 2 (new_data = false) with the HARQ soft buffer: the
     combined retransmission decodes, as the reference with its rx_buffer."""
