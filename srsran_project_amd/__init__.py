@@ -149,3 +149,13 @@ from .srs import (  # noqa: F401,E402
     srs_information,
     srs_validate,
 )
+from . import csi_rs  # noqa: F401,E402
+from .csi_rs import (  # noqa: F401,E402
+    CsiRsBatch,
+    CsiRsConfig,
+    CsiRsGenerator,
+    CsiRsPattern,
+    csi_rs_pattern,
+    csi_rs_reserved,
+    csi_rs_validate,
+)
