@@ -10,6 +10,7 @@
 #include "csi_rs_args.h"
 #include "device_buffer.h"
 #include "gold_sequence.h"
+#include "staged_call.h"
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -224,6 +225,7 @@ struct srs_amd_csi_rs_generator {
   pinned_stage  stage;
   stream_order  order;
   std::mutex    mtx;
+  std::mutex    host_mtx; // the host form's buffer and stream
 
   ~srs_amd_csi_rs_generator()
   {
@@ -414,33 +416,17 @@ int srs_amd_csi_rs_map_slot(srs_amd_csi_rs_generator*    gen,
 
   hipStream_t                 s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lock(gen->mtx);
-  hipError_t                  e = hipSetDevice(gen->device);
-  if (e != hipSuccess) {
-    return hip_fail(e, "CSI-RS generator device");
+  const size_t                bytes = items.size() * sizeof(csi_rs_item);
+  staged_call call("CSI-RS generator", gen->device, gen->descriptors, bytes, gen->stage, bytes, gen->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  const size_t bytes = items.size() * sizeof(csi_rs_item);
-  e                  = gen->descriptors.ensure(bytes);
-  if (e == hipSuccess) {
-    e = gen->stage.acquire(bytes);
-  }
-  if (e == hipSuccess) {
-    e = gen->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "CSI-RS generator scratch");
-  }
-  call_scope scope(gen->order, nullptr, s);
-  std::memcpy(gen->stage.at<uint8_t>(0), items.data(), bytes);
-  e = gen->stage.upload(gen->descriptors.ptr, bytes, s);
+  std::memcpy(call.host(), items.data(), bytes);
+  hipError_t e = call.upload(gen->descriptors.ptr, bytes);
   if (e == hipSuccess) {
     e = launch_csi_rs_map(gen->descriptors.as<csi_rs_item>(), static_cast<uint32_t>(items.size()), gen->d_jump, s);
   }
-  const int        rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "CSI-RS generator launch");
-  const hipError_t ce = scope.close();
-  if (rc == SRS_AMD_OK && ce != hipSuccess) {
-    return hip_fail(ce, "CSI-RS generator completion event");
-  }
-  return rc;
+  return call.finish(e);
 }
 
 int srs_amd_csi_rs_map(srs_amd_csi_rs_generator*    gen,
@@ -458,32 +444,21 @@ int srs_amd_csi_rs_map(srs_amd_csi_rs_generator*    gen,
     return rc;
   }
   const size_t bytes = static_cast<size_t>(nof_ports) * CSI_RS_NSYMB * nof_subc * sizeof(uint32_t);
-  hipError_t   e     = hipSuccess;
-  {
-    std::lock_guard<std::mutex> lock(gen->mtx);
-    e = hipSetDevice(gen->device);
-    if (e == hipSuccess) {
-      e = gen->host_io.ensure(bytes);
-    }
-    if (e == hipSuccess) {
-      e = hipMemcpyAsync(gen->host_io.ptr, grid, bytes, hipMemcpyHostToDevice, gen->stream);
-    }
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "CSI-RS generator upload");
+  host_call    call("CSI-RS generator", gen->host_mtx, gen->device, gen->stream);
+  call.grow(gen->host_io, bytes);
+  call.in(gen->host_io.ptr, grid, bytes);
+  if (!call.ok()) {
+    return call.finish();
   }
   srs_amd_csi_rs_config c = *cfg;
   c.grid                  = 0;
   c.d_grid                = nullptr;
   rc = srs_amd_csi_rs_map_slot(gen, &c, 1, gen->host_io.as<uint32_t>(), 0, 1, nof_ports, nof_subc, gen->stream);
-  if (rc != SRS_AMD_OK) {
-    return rc;
+  if (rc == SRS_AMD_OK) {
+    call.out(grid, gen->host_io.ptr, bytes);
   }
-  e = hipMemcpyAsync(grid, gen->host_io.ptr, bytes, hipMemcpyDeviceToHost, gen->stream);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(gen->stream);
-  }
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "CSI-RS generator download");
+  return call.finish(rc);
 }
+
 
 } // extern "C"

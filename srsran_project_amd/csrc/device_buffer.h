@@ -78,7 +78,7 @@ struct geometry_cache {
 
 // Host wait for an event by polling hipEventQuery: the staging buffers of the slot forms wait here once per call for
 // their previous upload, which has normally completed or is about to; hipEventSynchronize could fall back to an
-// interrupt-driven wait whose wake-up occasionally took ~7 ms (one such step in twenty, tools/gpu_r04_bimodal.sh).
+// interrupt-driven wait whose wake-up occasionally took ~7 ms (one such step in twenty).
 inline hipError_t event_wait_spin(hipEvent_t ev)
 {
   for (;;) {
@@ -120,15 +120,6 @@ struct stream_order {
   }
 };
 
-// Fans independent launches of one call out over up to FAN_STREAMS helper streams and joins them back into
-// the caller's stream (events only, no host synchronisation): the small per-bucket LDPC launches of a
-// heterogeneous slot run concurrently instead of one after the other on a mostly idle GPU.
-// Lanes of the fan: the helper streams, then (with_main) the caller's stream itself.  Configuration (read once):
-// SRSRAN_AMD_FAN_STREAMS helpers (0..4, default 1), SRSRAN_AMD_FAN_MAIN=0 keeps the caller's stream out of the
-// fan (default: it is a lane), SRSRAN_AMD_FAN_PRIORITY=1 helpers at the highest stream priority.  Measured on the
-// 64-cell sch_slot step (tools/gpu_r04_fan.sh, three processes each): one helper + the caller's stream 0.844-0.849
-// ms; four helpers 1.05-1.12 ms (the helpers' hardware queues are assigned per process and collide); no helper
-// 1.00 ms; high-priority helpers 1.39-1.65 ms.
 // n bytes from pinned host memory h (hipHostMalloc) to device memory d on stream s, by a copy kernel (not the SDMA
 // engine; stream_probe.hip)
 hipError_t upload_pinned(void* d, const void* h, size_t n, hipStream_t s);
@@ -136,6 +127,15 @@ hipError_t upload_pinned(void* d, const void* h, size_t n, hipStream_t s);
 // true when kernels of streams a and b overlap (two spin kernels, host-synchronous; stream_probe.hip)
 hipError_t streams_run_concurrently(hipStream_t a, hipStream_t b, bool& concurrent);
 
+// Fans independent launches of one call out over up to FAN_STREAMS helper streams and joins them back into
+// the caller's stream (events only, no host synchronisation): the small per-bucket LDPC launches of a
+// heterogeneous slot run concurrently instead of one after the other on a mostly idle GPU.
+// Lanes of the fan: the helper streams, then (with_main) the caller's stream itself.  Configuration (read once):
+// SRSRAN_AMD_FAN_STREAMS helpers (0..4, default 1), SRSRAN_AMD_FAN_MAIN=0 keeps the caller's stream out of the
+// fan (default: it is a lane), SRSRAN_AMD_FAN_PRIORITY=1 helpers at the highest stream priority.  Measured on the
+// 64-cell sch_slot step (three processes each): one helper + the caller's stream 0.844-0.849 ms; four helpers
+// 1.05-1.12 ms (the helpers' hardware queues are assigned per process and collide); no helper 1.00 ms;
+// high-priority helpers 1.39-1.65 ms.
 struct stream_fan {
   static constexpr int FAN_STREAMS = 4;
   static constexpr int SPARES      = 6; // helpers found on the caller's queue, kept so the next one lands elsewhere
@@ -310,11 +310,10 @@ struct call_scope {
   }
 };
 
-// Host-built launch descriptors (per-item argument blocks of a slot call) staged in pinned memory and
-// uploaded on the call's stream: the buffer is rewritten only once its previous upload has completed.
-// Pinned host staging for per-call descriptor uploads: a ring of RING buffers, each rewritten only once its previous
-// upload has completed, so a call can stage its descriptors while up to RING - 1 earlier calls' uploads still wait
-// behind their stream's work (r06: the slot forms of consecutive batches no longer wait for each other on the host).
+// Pinned host staging for the host-built launch descriptors (per-item argument blocks) of a slot call, uploaded on the
+// call's stream: a ring of RING buffers, each rewritten only once its previous upload has completed, so a call can
+// stage its descriptors while up to RING - 1 earlier calls' uploads still wait behind their stream's work (the slot
+// forms of consecutive batches do not wait for each other on the host).
 struct pinned_stage {
   static constexpr int RING = 3;
   struct slot {

@@ -12,6 +12,7 @@
 #include "device_buffer.h"
 #include "gold_sequence.h"
 #include "pdcch_args.h"
+#include "staged_call.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -348,35 +349,24 @@ int srs_amd_pdcch_process_slot(srs_amd_pdcch_processor* proc,
   const size_t total   = o_cw + align_up(cw_total, 256);
   const size_t staged  = o_msg; // descriptors + payloads come from the host
   auto         s       = static_cast<hipStream_t>(stream);
-  hipError_t   e       = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->buf.ensure(total);
+  staged_call  call("PDCCH processor", proc->device, proc->buf, total, proc->stage, staged, proc->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e == hipSuccess) {
-    e = proc->stage.acquire(staged);
-  }
-  if (e == hipSuccess) {
-    e = proc->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PDCCH processor scratch");
-  }
-  call_scope scope(proc->order, nullptr, s);
   for (uint32_t i = 0; i != nof_pdus; ++i) {
     desc[i].payload_offset = i * SRS_AMD_PDCCH_MAX_PAYLOAD;
-    std::memcpy(proc->stage.at<uint8_t>(o_pay + desc[i].payload_offset), pdus[i].dci.payload,
-                pdus[i].dci.payload_size);
+    std::memcpy(call.host(o_pay + desc[i].payload_offset), pdus[i].dci.payload, pdus[i].dci.payload_size);
   }
-  std::memcpy(proc->stage.at<uint8_t>(0), desc.data(), sizeof(pdcch_desc) * nof_pdus);
-  auto* base = proc->buf.as<uint8_t>();
-  auto* d_desc = reinterpret_cast<const pdcch_desc*>(base);
-  e            = proc->stage.upload(base, staged, s);
+  std::memcpy(call.host(), desc.data(), sizeof(pdcch_desc) * nof_pdus);
+  auto*      base   = proc->buf.as<uint8_t>();
+  auto*      d_desc = reinterpret_cast<const pdcch_desc*>(base);
+  hipError_t e      = call.upload(base, staged);
   if (e == hipSuccess) {
     e = launch_pdcch_crc(d_desc, nof_pdus, base + o_pay, base + o_msg, s);
   }
-  int rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pdcch_crc_kernel launch");
+  int rc = SRS_AMD_OK;
   for (auto& g : groups) {
-    if (rc != SRS_AMD_OK) {
+    if (e != hipSuccess || rc != SRS_AMD_OK) {
       break;
     }
     srs_amd_polar_code* code = nullptr;
@@ -388,12 +378,10 @@ int srs_amd_pdcch_process_slot(srs_amd_pdcch_processor* proc,
                                       static_cast<uint32_t>(g.second.size()), stream);
     }
   }
-  if (rc == SRS_AMD_OK) {
-    e  = launch_pdcch_map(d_desc, nof_pdus, max_rb, max_symbols, base + o_cw, proc->d_jump, s);
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pdcch_map_kernel launch");
+  if (e == hipSuccess && rc == SRS_AMD_OK) {
+    e = launch_pdcch_map(d_desc, nof_pdus, max_rb, max_symbols, base + o_cw, proc->d_jump, s);
   }
-  const hipError_t done = scope.close();
-  return rc != SRS_AMD_OK ? rc : (done == hipSuccess ? SRS_AMD_OK : hip_fail(done, "PDCCH completion event"));
+  return call.finish(e, rc);
 }
 
 int srs_amd_pdcch_process(srs_amd_pdcch_processor* proc,
@@ -408,31 +396,22 @@ int srs_amd_pdcch_process(srs_amd_pdcch_processor* proc,
   if (pdu->dci.nof_ports > nof_ports) {
     return fail(SRS_AMD_EINVAL, "The grid has %u ports, the PDU precodes onto %u.", nof_ports, pdu->dci.nof_ports);
   }
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PDCCH processor grid");
-  }
-  e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  if (e != hipSuccess) {
-    return hip_fail(e, "PDCCH grid upload");
+  const size_t bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
+  host_call    call("PDCCH processor", proc->host_mtx, proc->device, proc->stream);
+  call.grow(proc->host_grid, bytes);
+  call.in(proc->host_grid.ptr, grid, bytes);
+  if (!call.ok()) {
+    return call.finish();
   }
   srs_amd_pdcch_pdu p = *pdu;
   p.grid              = 0;
   p.d_grid            = nullptr;
-  int rc = srs_amd_pdcch_process_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_subc, proc->stream);
+  const int rc = srs_amd_pdcch_process_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_subc, proc->stream);
   if (rc == SRS_AMD_OK) {
-    e  = hipMemcpyAsync(grid, proc->host_grid.ptr, bytes, hipMemcpyDeviceToHost, proc->stream);
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PDCCH grid download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
+    call.out(grid, proc->host_grid.ptr, bytes);
   }
-  return rc;
+  return call.finish(rc);
 }
+
 
 } // extern "C"

@@ -20,6 +20,7 @@
 #include "gold_sequence.h"
 #include "modulation_args.h"
 #include "pdsch_modulator_args.h"
+#include "staged_call.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -731,31 +732,21 @@ int srs_amd_pdsch_modulate_slot(srs_amd_pdsch_modulator*      mod,
   }
   auto                        s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lock(mod->mtx);
-  hipError_t                  e = hipSetDevice(mod->device);
-  if (e == hipSuccess) {
-    e = mod->slot_items.ensure(total);
+  staged_call call("PDSCH modulator slot", mod->device, mod->slot_items, total, mod->stage, total, mod->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e == hipSuccess) {
-    e = mod->stage.acquire(total);
-  }
-  if (e == hipSuccess) {
-    e = mod->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PDSCH modulator slot descriptors");
-  }
-  call_scope scope(mod->order, nullptr, s);
-  std::memcpy(mod->stage.at<pdsch_map_args>(0), maps.data(), sizeof(pdsch_map_args) * maps.size());
-  std::memcpy(mod->stage.at<dmrs_pdsch_args>(o_dmrs), dmrs.data(), sizeof(dmrs_pdsch_args) * dmrs.size());
+  std::memcpy(call.host(), maps.data(), sizeof(pdsch_map_args) * maps.size());
+  std::memcpy(call.host(o_dmrs), dmrs.data(), sizeof(dmrs_pdsch_args) * dmrs.size());
   auto* d = mod->slot_items.as<uint8_t>();
   for (size_t q = 0; q != ptrs.size(); ++q) {
     ptrs[q].w = reinterpret_cast<const float*>(d + o_w) + ptrs_woff[q];
   }
   if (!ptrs.empty()) {
-    std::memcpy(mod->stage.at<ptrs_pdsch_args>(o_ptrs), ptrs.data(), sizeof(ptrs_pdsch_args) * ptrs.size());
-    std::memcpy(mod->stage.at<float>(o_w), ptrs_w.data(), sizeof(float) * ptrs_w.size());
+    std::memcpy(call.host(o_ptrs), ptrs.data(), sizeof(ptrs_pdsch_args) * ptrs.size());
+    std::memcpy(call.host(o_w), ptrs_w.data(), sizeof(float) * ptrs_w.size());
   }
-  e       = mod->stage.upload(d, total, s);
+  hipError_t e = call.upload(d, total);
   if (e == hipSuccess) {
     e = launch_pdsch_map_items(reinterpret_cast<const pdsch_map_args*>(d), static_cast<uint32_t>(maps.size()),
                                max_tiles, max_symbols, s);
@@ -769,10 +760,9 @@ int srs_amd_pdsch_modulate_slot(srs_amd_pdsch_modulator*      mod,
     e = launch_dmrs_pdsch_items(reinterpret_cast<const dmrs_pdsch_args*>(d + o_dmrs),
                                 static_cast<uint32_t>(dmrs.size()), max_blocks, max_dmrs_symbols, s);
   }
-  const hipError_t done = scope.close();
-  e                     = e != hipSuccess ? e : done;
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PDSCH modulator slot launch");
+  return call.finish(e);
 }
+
 
 int srs_amd_ptrs_pdsch_reserved(const srs_amd_ptrs_pdsch_config* cfg, srs_amd_re_pattern* pattern)
 {

@@ -10,6 +10,7 @@
 #include "device_buffer.h"
 #include "dft_engine.h"
 #include "prach_args.h"
+#include "staged_call.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -207,6 +208,7 @@ struct srs_amd_prach_detector {
   pinned_stage  stage;
   stream_order  order;
   std::mutex    mtx;
+  std::mutex    host_mtx; // the host form's buffer and stream
 
   ~srs_amd_prach_detector()
   {
@@ -383,21 +385,16 @@ int srs_amd_prach_detect_batch(srs_amd_prach_detector*     det,
     o.time_resolution_s  = quantize_time(1.0 / o.sampling_rate);
     o.time_advance_max_s = quantize_time(static_cast<double>(g.max_delay_samples) * 0.8 / o.sampling_rate);
   }
-  if (e == hipSuccess) {
-    e = det->descriptors.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = det->stage.acquire(bytes);
-  }
-  if (e == hipSuccess) {
-    e = det->order.begin(s);
-  }
   if (e != hipSuccess) {
     return hip_fail(e, "PRACH detector scratch");
   }
-  call_scope scope(det->order, nullptr, s);
-  std::memcpy(det->stage.at<uint8_t>(0), occ.data(), bytes);
-  e = det->stage.upload(det->descriptors.ptr, bytes, s);
+  staged_call call("PRACH detector", staged_call::DEVICE_IS_CURRENT, det->descriptors, bytes, det->stage, bytes,
+                   det->order, s);
+  if (!call.ok()) {
+    return call.finish();
+  }
+  std::memcpy(call.host(), occ.data(), bytes);
+  e = call.upload(det->descriptors.ptr, bytes);
   const prach_occasion* d_occ = det->descriptors.as<prach_occasion>();
   for (uint32_t k = 0; k != NOF_IDFT_SIZES && e == hipSuccess; ++k) {
     e = launch_prach_correlate(d_occ + group_begin[k], group_begin[k + 1] - group_begin[k], IDFT_SIZES[k], s);
@@ -405,12 +402,7 @@ int srs_amd_prach_detect_batch(srs_amd_prach_detector*     det,
   if (e == hipSuccess) {
     e = launch_prach_finish(d_occ, nof_occasions, s);
   }
-  const int        rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PRACH detector launch");
-  const hipError_t ce = scope.close();
-  if (rc == SRS_AMD_OK && ce != hipSuccess) {
-    return hip_fail(ce, "PRACH detector completion event");
-  }
-  return rc;
+  return call.finish(e);
 }
 
 int srs_amd_prach_detect(srs_amd_prach_detector*     det,
@@ -428,31 +420,20 @@ int srs_amd_prach_detect(srs_amd_prach_detector*     det,
   }
   const size_t in_bytes = d.g.nof_elements * sizeof(uint32_t);
   const size_t res_off  = align_up(in_bytes, 16);
-  hipError_t   e        = hipSuccess;
-  {
-    std::lock_guard<std::mutex> lock(det->mtx);
-    e = hipSetDevice(det->device);
-    if (e == hipSuccess) {
-      e = det->host_io.ensure(res_off + sizeof(srs_amd_prach_result));
-    }
-    if (e == hipSuccess) {
-      e = hipMemcpyAsync(det->host_io.ptr, symbols, in_bytes, hipMemcpyHostToDevice, det->stream);
-    }
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PRACH detector upload");
+  host_call    call("PRACH detector", det->host_mtx, det->device, det->stream);
+  call.grow(det->host_io, res_off + sizeof(srs_amd_prach_result));
+  call.in(det->host_io.ptr, symbols, in_bytes);
+  if (!call.ok()) {
+    return call.finish();
   }
   auto*          d_res  = reinterpret_cast<srs_amd_prach_result*>(det->host_io.as<uint8_t>() + res_off);
   const uint64_t offset = 0;
   rc = srs_amd_prach_detect_batch(det, config, 1, det->host_io.ptr, &offset, d_res, det->stream);
-  if (rc != SRS_AMD_OK) {
-    return rc;
+  if (rc == SRS_AMD_OK) {
+    call.out(result, d_res, sizeof(srs_amd_prach_result));
   }
-  e = hipMemcpyAsync(result, d_res, sizeof(srs_amd_prach_result), hipMemcpyDeviceToHost, det->stream);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(det->stream);
-  }
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PRACH detector download");
+  return call.finish(rc);
 }
+
 
 } // extern "C"

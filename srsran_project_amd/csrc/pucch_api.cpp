@@ -21,6 +21,7 @@
 #include "device_buffer.h"
 #include "gold_sequence.h"
 #include "pucch_args.h"
+#include "staged_call.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -236,6 +237,45 @@ uint32_t uci_crc_bits(uint32_t A, uint32_t E)
   return C * L;
 }
 
+// The checks every slot entry point opens with; false: the entry point returns rc (an error, or SRS_AMD_OK for an
+// empty call).
+bool slot_entry(const void* proc, uint32_t nof, bool have_args, uint32_t nof_subc, int& rc)
+{
+  if (proc == nullptr || (nof != 0 && !have_args)) {
+    rc = fail(SRS_AMD_EINVAL, "null argument");
+  } else if (nof == 0) {
+    rc = SRS_AMD_OK;
+  } else if (nof_subc == 0 || nof_subc % 12 != 0) {
+    rc = fail(SRS_AMD_EINVAL, "Invalid number of grid subcarriers (i.e., %u).", nof_subc);
+  } else {
+    return true;
+  }
+  return false;
+}
+
+// Resets the descriptor d of PDU (or Format 1 batch) p and fills its grid fields: the PDU's own grid or grid p.grid
+// of the slot call's array, and the receive ports, each checked against the grid's.
+template <typename Desc, typename Pdu>
+int resolve_grid(const Pdu& p, const uint32_t* d_grids, uint64_t grid_stride, uint32_t nof_grids,
+                 uint32_t nof_grid_ports, uint32_t nof_subc, Desc& d)
+{
+  if (p.d_grid == nullptr && (d_grids == nullptr || p.grid >= nof_grids)) {
+    return fail(SRS_AMD_EINVAL, "grid index %u out of range (or no grid).", p.grid);
+  }
+  d             = Desc{};
+  d.grid        = p.d_grid != nullptr ? p.d_grid : d_grids + p.grid * grid_stride;
+  d.port_stride = NSYMB * nof_subc;
+  d.nof_subc    = nof_subc;
+  d.nof_ports   = p.nof_ports;
+  for (uint32_t i = 0; i != p.nof_ports; ++i) {
+    if (p.ports[i] >= nof_grid_ports) {
+      return fail(SRS_AMD_EINVAL, "port %u outside the grid's %u ports.", p.ports[i], nof_grid_ports);
+    }
+    d.ports[i] = p.ports[i];
+  }
+  return SRS_AMD_OK;
+}
+
 int make_f2_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f2_pdu& p, const uint32_t* d_grids,
                  uint64_t grid_stride, uint32_t nof_grids, uint32_t nof_grid_ports, uint32_t nof_subc,
                  pucch_f2_desc& d)
@@ -277,26 +317,16 @@ int make_f2_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f2_pdu
   if (static_cast<float>(K + uci_crc_bits(K, E)) / static_cast<float>(E) > 0.80F) {
     return fail(SRS_AMD_EINVAL, "The effective code rate exceeds the maximum allowed 0.8.");
   }
-  if (p.d_grid == nullptr && (d_grids == nullptr || p.grid >= nof_grids)) {
-    return fail(SRS_AMD_EINVAL, "grid index %u out of range (or no grid).", p.grid);
+  const int rc = resolve_grid(p, d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, d);
+  if (rc != SRS_AMD_OK) {
+    return rc;
   }
-  d             = pucch_f2_desc{};
-  d.grid        = p.d_grid != nullptr ? p.d_grid : d_grids + p.grid * grid_stride;
-  d.port_stride = NSYMB * nof_subc;
-  d.nof_subc    = nof_subc;
-  d.l0          = p.start_symbol_index;
-  d.nsym        = p.nof_symbols;
-  d.hop         = p.second_hop_prb >= 0 ? 1u : 0u;
-  d.nof_prb     = p.nof_prb;
-  d.prb[0]      = p.bwp_start_rb + p.starting_prb;
-  d.prb[1]      = d.hop ? p.bwp_start_rb + static_cast<uint32_t>(p.second_hop_prb) : d.prb[0];
-  d.nof_ports   = p.nof_ports;
-  for (uint32_t i = 0; i != p.nof_ports; ++i) {
-    if (p.ports[i] >= nof_grid_ports) {
-      return fail(SRS_AMD_EINVAL, "port %u outside the grid's %u ports.", p.ports[i], nof_grid_ports);
-    }
-    d.ports[i] = p.ports[i];
-  }
+  d.l0      = p.start_symbol_index;
+  d.nsym    = p.nof_symbols;
+  d.hop     = p.second_hop_prb >= 0 ? 1u : 0u;
+  d.nof_prb = p.nof_prb;
+  d.prb[0]  = p.bwp_start_rb + p.starting_prb;
+  d.prb[1]  = d.hop ? p.bwp_start_rb + static_cast<uint32_t>(p.second_hop_prb) : d.prb[0];
   float epoch[NSYMB];
   symbol_epochs(p.numerology, epoch);
   const uint32_t np = 4 * p.nof_prb;
@@ -421,27 +451,17 @@ int make_f34_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f34_p
   if (static_cast<float>(K + uci_crc_bits(K, e_tot)) / static_cast<float>(chan) > 0.80F) {
     return fail(SRS_AMD_EINVAL, "The effective code rate exceeds the maximum allowed 0.8.");
   }
-  if (p.d_grid == nullptr && (d_grids == nullptr || p.grid >= nof_grids)) {
-    return fail(SRS_AMD_EINVAL, "grid index %u out of range (or no grid).", p.grid);
+  const int rc = resolve_grid(p, d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, d);
+  if (rc != SRS_AMD_OK) {
+    return rc;
   }
-  d             = pucch_f34_desc{};
-  d.grid        = p.d_grid != nullptr ? p.d_grid : d_grids + p.grid * grid_stride;
-  d.port_stride = NSYMB * nof_subc;
-  d.nof_subc    = nof_subc;
-  d.l0          = p.start_symbol_index;
-  d.nsym        = p.nof_symbols;
-  d.M           = M;
-  d.dmrs_mask   = mask;
-  d.hop_sym     = hop ? p.nof_symbols / 2 : p.nof_symbols;
-  d.subc0[0]    = 12 * (p.bwp_start_rb + p.starting_prb);
-  d.subc0[1]    = hop ? 12 * (p.bwp_start_rb + static_cast<uint32_t>(p.second_hop_prb)) : d.subc0[0];
-  d.nof_ports   = p.nof_ports;
-  for (uint32_t i = 0; i != p.nof_ports; ++i) {
-    if (p.ports[i] >= nof_grid_ports) {
-      return fail(SRS_AMD_EINVAL, "port %u outside the grid's %u ports.", p.ports[i], nof_grid_ports);
-    }
-    d.ports[i] = p.ports[i];
-  }
+  d.l0        = p.start_symbol_index;
+  d.nsym      = p.nof_symbols;
+  d.M         = M;
+  d.dmrs_mask = mask;
+  d.hop_sym   = hop ? p.nof_symbols / 2 : p.nof_symbols;
+  d.subc0[0]  = 12 * (p.bwp_start_rb + p.starting_prb);
+  d.subc0[1]  = hop ? 12 * (p.bwp_start_rb + static_cast<uint32_t>(p.second_hop_prb)) : d.subc0[0];
   float epoch[NSYMB];
   symbol_epochs(p.numerology, epoch);
   for (uint32_t r = 0; r != p.nof_symbols; ++r) {
@@ -498,6 +518,71 @@ int make_f34_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f34_p
   return SRS_AMD_OK;
 }
 
+// Decoder order of a slot's PDUs: grouped by (payload, codeword, modulation) size, one UCI decoder launch per group.
+std::vector<uint32_t> decode_order(const std::vector<uint32_t>& K, const std::vector<uint32_t>& E,
+                                   const std::vector<uint32_t>& Q)
+{
+  std::vector<uint32_t> perm(K.size());
+  std::iota(perm.begin(), perm.end(), 0u);
+  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
+    return K[a] != K[b] ? K[a] < K[b] : (E[a] != E[b] ? E[a] < E[b] : Q[a] < Q[b]);
+  });
+  return perm;
+}
+
+// proc->work of a Format 2 / 3 / 4 slot call, rows in decoder order: LLRs (rows of `row`) | messages | decoder status
+struct uci_work {
+  uint32_t row, msg_stride;
+  int8_t*  llr;
+  uint8_t* msg;
+  int32_t* status;
+};
+
+// Makes the device current and grows proc->work for the PDUs of payload sizes K.
+hipError_t uci_work_layout(srs_amd_pucch_processor* proc, const std::vector<uint32_t>& K, uint32_t row, uci_work& w)
+{
+  const uint32_t max_k     = *std::max_element(K.begin(), K.end());
+  w.row                    = row;
+  w.msg_stride             = (std::max(max_k, 1u) + 63) / 64 * 64;
+  const size_t     llr_bytes = K.size() * static_cast<size_t>(row);
+  const size_t     msg_bytes = K.size() * static_cast<size_t>(w.msg_stride);
+  hipError_t       e         = hipSetDevice(proc->device);
+  if (e == hipSuccess) {
+    e = proc->work.ensure(llr_bytes + msg_bytes + K.size() * sizeof(int32_t));
+  }
+  w.llr    = proc->work.as<int8_t>();
+  w.msg    = proc->work.as<uint8_t>() + llr_bytes;
+  w.status = reinterpret_cast<int32_t*>(w.msg + msg_bytes);
+  return e;
+}
+
+// The UCI decode of a slot call after its demodulation kernel: one decoder launch per group of the decoder order
+// perm, then the results and payloads back in PDU order (d_perm: perm, then the payload sizes, in device memory).
+int uci_decode_tail(srs_amd_pucch_processor* proc, const uci_work& w, const std::vector<uint32_t>& K,
+                    const std::vector<uint32_t>& E, const std::vector<uint32_t>& Q, const std::vector<uint32_t>& perm,
+                    const uint32_t* d_perm, srs_amd_pucch_uci_result* d_results, uint8_t* d_payloads,
+                    uint64_t payload_stride, hipStream_t s)
+{
+  const uint32_t nof_pdus = static_cast<uint32_t>(perm.size());
+  for (uint32_t j0 = 0; j0 != nof_pdus;) {
+    const uint32_t i0 = perm[j0];
+    uint32_t       j1 = j0 + 1;
+    while (j1 != nof_pdus && K[perm[j1]] == K[i0] && E[perm[j1]] == E[i0] && Q[perm[j1]] == Q[i0]) {
+      ++j1;
+    }
+    const int rc = srs_amd_uci_decode_batch(proc->uci, w.llr + static_cast<size_t>(j0) * w.row, w.row, E[i0], K[i0],
+                                            static_cast<int32_t>(Q[i0]), w.msg + static_cast<size_t>(j0) * w.msg_stride,
+                                            w.msg_stride, w.status + j0, sizeof(int32_t), j1 - j0, s);
+    if (rc != SRS_AMD_OK) {
+      return rc;
+    }
+    j0 = j1;
+  }
+  const hipError_t e = launch_pucch_uci_finish(w.status, w.msg, w.msg_stride, d_perm, d_perm + nof_pdus, nof_pdus,
+                                               d_results, d_payloads, payload_stride, s);
+  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_uci_finish_kernel launch");
+}
+
 // The Format 3 / 4 slot form; decode = false stops after the LLRs (rows of PUCCH_F3_MAX_E in proc->work).
 int f34_slot(srs_amd_pucch_processor*     proc,
              const srs_amd_pucch_f34_pdu* pdus,
@@ -513,24 +598,18 @@ int f34_slot(srs_amd_pucch_processor*     proc,
              void*                        stream,
              bool                         decode)
 {
-  if (proc == nullptr || (nof_pdus != 0 && (pdus == nullptr || d_results == nullptr || d_payloads == nullptr))) {
-    return fail(SRS_AMD_EINVAL, "null argument");
-  }
-  if (nof_pdus == 0) {
-    return SRS_AMD_OK;
-  }
-  if (nof_subc == 0 || nof_subc % 12 != 0) {
-    return fail(SRS_AMD_EINVAL, "Invalid number of grid subcarriers (i.e., %u).", nof_subc);
+  int rc = SRS_AMD_OK;
+  if (!slot_entry(proc, nof_pdus, pdus != nullptr && d_results != nullptr && d_payloads != nullptr, nof_subc, rc)) {
+    return rc;
   }
   std::lock_guard<std::mutex>        lock(proc->mtx);
   std::vector<pucch_f34_desc>        desc(nof_pdus);
   std::vector<std::vector<float2>>   pil(nof_pdus);
   std::vector<std::vector<uint32_t>> scr(nof_pdus);
   std::vector<uint32_t>              K(nof_pdus), E(nof_pdus), Q(nof_pdus);
-  uint32_t                           max_k = 0;
   for (uint32_t i = 0; i != nof_pdus; ++i) {
-    const int rc = make_f34_desc(proc, pdus[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, desc[i],
-                                 pil[i], scr[i], E[i], K[i]);
+    rc = make_f34_desc(proc, pdus[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, desc[i], pil[i],
+                       scr[i], E[i], K[i]);
     if (rc != SRS_AMD_OK) {
       return rc;
     }
@@ -538,29 +617,15 @@ int f34_slot(srs_amd_pucch_processor*     proc,
       return fail(SRS_AMD_EINVAL, "payload_stride %llu below the PDU's %u payload bits.",
                   static_cast<unsigned long long>(payload_stride), K[i]);
     }
-    Q[i]  = pdus[i].pi2_bpsk ? 0u : 2u;
-    max_k = std::max(max_k, K[i]);
+    Q[i] = pdus[i].pi2_bpsk ? 0u : 2u;
   }
-  std::vector<uint32_t> perm(nof_pdus);
-  std::iota(perm.begin(), perm.end(), 0u);
-  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
-    return K[a] != K[b] ? K[a] < K[b] : (E[a] != E[b] ? E[a] < E[b] : Q[a] < Q[b]);
-  });
-  const uint32_t msg_stride = (std::max(max_k, 1u) + 63) / 64 * 64;
-  const size_t   llr_bytes  = static_cast<size_t>(nof_pdus) * PUCCH_F3_MAX_E;
-  const size_t   msg_bytes  = static_cast<size_t>(nof_pdus) * msg_stride;
-  const size_t   st_bytes   = static_cast<size_t>(nof_pdus) * sizeof(int32_t);
-  auto           s          = static_cast<hipStream_t>(stream);
-  hipError_t     e          = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->work.ensure(llr_bytes + msg_bytes + st_bytes);
+  const std::vector<uint32_t> perm = decode_order(K, E, Q);
+  auto                        s    = static_cast<hipStream_t>(stream);
+  uci_work                    w;
+  const hipError_t            we = uci_work_layout(proc, K, PUCCH_F3_MAX_E, w);
+  if (we != hipSuccess) {
+    return hip_fail(we, "PUCCH processor scratch");
   }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH processor scratch");
-  }
-  int8_t*  d_llr = proc->work.as<int8_t>();
-  uint8_t* d_msg = proc->work.as<uint8_t>() + llr_bytes;
-  int32_t* d_st  = reinterpret_cast<int32_t*>(proc->work.as<uint8_t>() + llr_bytes + msg_bytes);
   // stage layout: descriptors (decoder order), perm, nbits, then every PDU's DM-RS and scrambling words
   const size_t dbytes = sizeof(pucch_f34_desc) * nof_pdus;
   const size_t ioff   = (dbytes + 255) & ~size_t(255);
@@ -574,61 +639,34 @@ int f34_slot(srs_amd_pucch_processor*     proc,
     off        = (off + scr[i].size() * sizeof(uint32_t) + 15) & ~size_t(15);
   }
   const size_t bytes = off;
-  if (e == hipSuccess) {
-    e = proc->buf.ensure(bytes);
+  staged_call  call("PUCCH processor", staged_call::DEVICE_IS_CURRENT, proc->buf, bytes, proc->stage, bytes,
+                    proc->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e == hipSuccess) {
-    e = proc->stage.acquire(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH processor scratch");
-  }
-  std::vector<pucch_f34_desc> ordered(nof_pdus);
-  std::vector<uint32_t>       nbits(nof_pdus);
+  auto* ordered = call.host<pucch_f34_desc>();
+  auto* h_perm  = call.host<uint32_t>(ioff);
   for (uint32_t j = 0; j != nof_pdus; ++j) {
     const uint32_t i = perm[j];
     ordered[j]       = desc[i];
     ordered[j].pil    = reinterpret_cast<const float2*>(proc->buf.as<uint8_t>() + pil_off[i]);
     ordered[j].scr    = reinterpret_cast<const uint32_t*>(proc->buf.as<uint8_t>() + scr_off[i]);
-    ordered[j].llr    = d_llr + static_cast<size_t>(j) * PUCCH_F3_MAX_E;
+    ordered[j].llr    = w.llr + static_cast<size_t>(j) * PUCCH_F3_MAX_E;
     ordered[j].result = d_results + i;
-    nbits[j]          = K[i];
+    h_perm[j]            = i;
+    h_perm[nof_pdus + j] = K[i];
+    std::memcpy(call.host(pil_off[i]), pil[i].data(), pil[i].size() * sizeof(float2));
+    std::memcpy(call.host(scr_off[i]), scr[i].data(), scr[i].size() * sizeof(uint32_t));
   }
-  call_scope scope(proc->order, nullptr, s);
-  std::memcpy(proc->stage.at<uint8_t>(0), ordered.data(), dbytes);
-  std::memcpy(proc->stage.at<uint8_t>(ioff), perm.data(), ibytes);
-  std::memcpy(proc->stage.at<uint8_t>(ioff + ibytes), nbits.data(), ibytes);
-  for (uint32_t i = 0; i != nof_pdus; ++i) {
-    std::memcpy(proc->stage.at<uint8_t>(pil_off[i]), pil[i].data(), pil[i].size() * sizeof(float2));
-    std::memcpy(proc->stage.at<uint8_t>(scr_off[i]), scr[i].data(), scr[i].size() * sizeof(uint32_t));
-  }
-  e = proc->stage.upload(proc->buf.ptr, bytes, s);
+  hipError_t e = call.upload(proc->buf.ptr, bytes);
   if (e == hipSuccess) {
     e = launch_pucch_f34(proc->buf.as<pucch_f34_desc>(), nof_pdus, s);
   }
-  int rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_f34_kernel launch");
-  for (uint32_t j0 = 0; decode && rc == SRS_AMD_OK && j0 != nof_pdus;) {
-    const uint32_t i0 = perm[j0];
-    uint32_t       j1 = j0 + 1;
-    while (j1 != nof_pdus && K[perm[j1]] == K[i0] && E[perm[j1]] == E[i0] && Q[perm[j1]] == Q[i0]) {
-      ++j1;
-    }
-    rc = srs_amd_uci_decode_batch(proc->uci, d_llr + static_cast<size_t>(j0) * PUCCH_F3_MAX_E, PUCCH_F3_MAX_E, E[i0],
-                                  K[i0], static_cast<int32_t>(Q[i0]), d_msg + static_cast<size_t>(j0) * msg_stride,
-                                  msg_stride, d_st + j0, sizeof(int32_t), j1 - j0, s);
-    j0 = j1;
+  if (decode && e == hipSuccess) {
+    rc = uci_decode_tail(proc, w, K, E, Q, perm, reinterpret_cast<const uint32_t*>(proc->buf.as<uint8_t>() + ioff),
+                         d_results, d_payloads, payload_stride, s);
   }
-  if (decode && rc == SRS_AMD_OK) {
-    const uint32_t* d_perm = reinterpret_cast<const uint32_t*>(proc->buf.as<uint8_t>() + ioff);
-    e  = launch_pucch_uci_finish(d_st, d_msg, msg_stride, d_perm, d_perm + nof_pdus, nof_pdus, d_results, d_payloads,
-                                 payload_stride, s);
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_uci_finish_kernel launch");
-  }
-  const hipError_t done = scope.close();
-  return rc != SRS_AMD_OK ? rc : (done == hipSuccess ? SRS_AMD_OK : hip_fail(done, "PUCCH completion event"));
+  return call.finish(e, rc);
 }
 
 int make_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f0_pdu& p, const uint32_t* d_grids,
@@ -649,28 +687,18 @@ int make_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f0_pdu& p
   if (p.nof_harq_ack == 0 && !p.sr_opportunity) {
     return fail(SRS_AMD_EINVAL, "Invalid payload combination.");
   }
-  if (p.d_grid == nullptr && (d_grids == nullptr || p.grid >= nof_grids)) {
-    return fail(SRS_AMD_EINVAL, "grid index %u out of range (or no grid).", p.grid);
+  const int rc = resolve_grid(p, d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, d);
+  if (rc != SRS_AMD_OK) {
+    return rc;
   }
-  d      = pucch_f0_desc{};
-  d.grid = p.d_grid != nullptr ? p.d_grid : d_grids + p.grid * grid_stride;
-  d.port_stride = NSYMB * nof_subc;
-  d.nof_subc    = nof_subc;
-  d.l0          = p.start_symbol_index;
-  d.nsym        = p.nof_symbols;
+  d.l0   = p.start_symbol_index;
+  d.nsym = p.nof_symbols;
   for (uint32_t l = 0; l != p.nof_symbols; ++l) {
     const uint32_t prb = (l != 0 && p.second_hop_prb >= 0) ? static_cast<uint32_t>(p.second_hop_prb) : p.starting_prb;
     if (12 * (prb + 1) > nof_subc) {
       return fail(SRS_AMD_EINVAL, "PRB %u outside the grid.", prb);
     }
     d.subc0[l] = 12 * prb;
-  }
-  d.nof_ports = p.nof_ports;
-  for (uint32_t i = 0; i != p.nof_ports; ++i) {
-    if (p.ports[i] >= nof_grid_ports) {
-      return fail(SRS_AMD_EINVAL, "port %u outside the grid's %u ports.", p.ports[i], nof_grid_ports);
-    }
-    d.ports[i] = p.ports[i];
   }
   const f0_entry* tab = T_SR;
   uint32_t        n   = 1;
@@ -735,29 +763,19 @@ int make_f1_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f1_bat
   if (b.nof_entries == 0 || b.nof_entries > PUCCH_F1_MAX_ENTRIES || b.entries == nullptr) {
     return fail(SRS_AMD_EINVAL, "Invalid number of multiplexed PUCCH (i.e., %u).", b.nof_entries);
   }
-  if (b.d_grid == nullptr && (d_grids == nullptr || b.grid >= nof_grids)) {
-    return fail(SRS_AMD_EINVAL, "grid index %u out of range (or no grid).", b.grid);
+  const int rc = resolve_grid(b, d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, d);
+  if (rc != SRS_AMD_OK) {
+    return rc;
   }
-  d             = pucch_f1_desc{};
-  d.grid        = b.d_grid != nullptr ? b.d_grid : d_grids + b.grid * grid_stride;
-  d.port_stride = NSYMB * nof_subc;
-  d.nof_subc    = nof_subc;
-  d.l0          = b.start_symbol_index;
-  d.nsym        = b.nof_symbols;
-  d.nof_hops    = hops;
+  d.l0       = b.start_symbol_index;
+  d.nsym     = b.nof_symbols;
+  d.nof_hops = hops;
   for (uint32_t h = 0; h != hops; ++h) {
     const uint32_t prb = h == 0 ? b.starting_prb : static_cast<uint32_t>(b.second_hop_prb);
     if (prb > 274 || 12 * (prb + 1) > nof_subc) {
       return fail(SRS_AMD_EINVAL, "PRB %u outside the grid.", prb);
     }
     d.subc0[h] = 12 * prb;
-  }
-  d.nof_ports = b.nof_ports;
-  for (uint32_t i = 0; i != b.nof_ports; ++i) {
-    if (b.ports[i] >= nof_grid_ports) {
-      return fail(SRS_AMD_EINVAL, "port %u outside the grid's %u ports.", b.ports[i], nof_grid_ports);
-    }
-    d.ports[i] = b.ports[i];
   }
   const uint32_t occ_ratio = hops == 2 ? 4u : 2u;
   uint32_t       used[7]   = {};
@@ -789,6 +807,157 @@ int make_f1_desc(const srs_amd_pucch_processor* proc, const srs_amd_pucch_f1_bat
     d.base[k] = make_float2(base[2 * k], base[2 * k + 1]);
   }
   return SRS_AMD_OK;
+}
+
+// The Format 2 slot form; decode = false stops after the LLRs (rows of PUCCH_F2_MAX_E in proc->work, decoder order).
+int f2_slot(srs_amd_pucch_processor*    proc,
+            const srs_amd_pucch_f2_pdu* pdus,
+            uint32_t                    nof_pdus,
+            const uint32_t*             d_grids,
+            uint64_t                    grid_stride,
+            uint32_t                    nof_grids,
+            uint32_t                    nof_grid_ports,
+            uint32_t                    nof_subc,
+            srs_amd_pucch_uci_result*   d_results,
+            uint8_t*                    d_payloads,
+            uint64_t                    payload_stride,
+            void*                       stream,
+            bool                        decode)
+{
+  int rc = SRS_AMD_OK;
+  if (!slot_entry(proc, nof_pdus, pdus != nullptr && d_results != nullptr && d_payloads != nullptr, nof_subc, rc)) {
+    return rc;
+  }
+  std::lock_guard<std::mutex> lock(proc->mtx);
+  std::vector<uint32_t>       K(nof_pdus), E(nof_pdus), Q(nof_pdus, 2u); // QPSK
+  for (uint32_t i = 0; i != nof_pdus; ++i) {
+    const srs_amd_pucch_f2_pdu& p = pdus[i];
+    K[i] = p.nof_harq_ack + p.nof_sr + p.nof_csi_part1 + p.nof_csi_part2;
+    E[i] = 16 * p.nof_prb * p.nof_symbols;
+    if (K[i] > payload_stride) {
+      return fail(SRS_AMD_EINVAL, "payload_stride %llu below the PDU's %u payload bits.",
+                  static_cast<unsigned long long>(payload_stride), K[i]);
+    }
+  }
+  const std::vector<uint32_t> perm = decode_order(K, E, Q);
+  auto                        s    = static_cast<hipStream_t>(stream);
+  uci_work                    w;
+  const hipError_t            we = uci_work_layout(proc, K, PUCCH_F2_MAX_E, w);
+  if (we != hipSuccess) {
+    return hip_fail(we, "PUCCH processor scratch");
+  }
+  std::vector<pucch_f2_desc> desc(nof_pdus);
+  for (uint32_t j = 0; j != nof_pdus; ++j) {
+    const uint32_t i = perm[j];
+    rc = make_f2_desc(proc, pdus[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, desc[j]);
+    if (rc != SRS_AMD_OK) {
+      return rc;
+    }
+    desc[j].llr    = w.llr + static_cast<size_t>(j) * PUCCH_F2_MAX_E;
+    desc[j].result = d_results + i;
+  }
+  // stage layout: descriptors (decoder order), perm, nbits
+  const size_t dbytes = sizeof(pucch_f2_desc) * nof_pdus;
+  const size_t ioff   = (dbytes + 255) & ~size_t(255);
+  const size_t bytes  = ioff + 2 * sizeof(uint32_t) * nof_pdus;
+  staged_call  call("PUCCH processor", staged_call::DEVICE_IS_CURRENT, proc->buf, bytes, proc->stage, bytes,
+                    proc->order, s);
+  if (!call.ok()) {
+    return call.finish();
+  }
+  std::memcpy(call.host(), desc.data(), dbytes);
+  auto* h_perm = call.host<uint32_t>(ioff);
+  for (uint32_t j = 0; j != nof_pdus; ++j) {
+    h_perm[j]            = perm[j];
+    h_perm[nof_pdus + j] = K[perm[j]];
+  }
+  hipError_t e = call.upload(proc->buf.ptr, bytes);
+  if (e == hipSuccess) {
+    e = launch_pucch_f2(proc->buf.as<pucch_f2_desc>(), nof_pdus, s);
+  }
+  if (decode && e == hipSuccess) {
+    rc = uci_decode_tail(proc, w, K, E, Q, perm, reinterpret_cast<const uint32_t*>(proc->buf.as<uint8_t>() + ioff),
+                         d_results, d_payloads, payload_stride, s);
+  }
+  return call.finish(e, rc);
+}
+
+// A host form: the grid up to the processor's private buffers, one PDU (or Format 1 batch) on that grid through
+// slot(p) on the private stream, then download(call, p) queues the results back.
+template <typename Pdu, typename Slot, typename Download>
+int host_form(srs_amd_pucch_processor* proc, const Pdu* pdu, const uint32_t* grid, uint32_t nof_ports,
+              uint32_t nof_subc, size_t res_bytes, size_t payload_bytes, Slot slot, Download download)
+{
+  const size_t bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
+  host_call    call("PUCCH processor", proc->host_mtx, proc->device, proc->stream);
+  call.grow(proc->host_grid, bytes);
+  call.grow(proc->host_res, res_bytes);
+  call.grow(proc->host_payload, payload_bytes);
+  call.in(proc->host_grid.ptr, grid, bytes);
+  if (!call.ok()) {
+    return call.finish();
+  }
+  Pdu p    = *pdu;
+  p.grid   = 0;
+  p.d_grid = nullptr;
+  const int rc = slot(p);
+  if (rc == SRS_AMD_OK) {
+    download(call, p);
+  }
+  return call.finish(rc);
+}
+
+// Host forms of Formats 2 / 3 / 4 over their slot form `slot`: the result and payload down, or with llrs the first
+// llr_len(p) LLRs of the demodulation alone.
+template <typename Pdu, typename Slot, typename LlrLen>
+int uci_host(srs_amd_pucch_processor* proc, const Pdu* pdu, const uint32_t* grid, uint32_t nof_ports,
+             uint32_t nof_subc, srs_amd_pucch_uci_result* result, uint8_t* payload, int8_t* llrs,
+             uint32_t payload_stride, Slot slot, LlrLen llr_len)
+{
+  if (proc == nullptr || pdu == nullptr || grid == nullptr ||
+      (llrs == nullptr && (result == nullptr || payload == nullptr))) {
+    return fail(SRS_AMD_EINVAL, "null argument");
+  }
+  const uint32_t K = pdu->nof_harq_ack + pdu->nof_sr + pdu->nof_csi_part1 + pdu->nof_csi_part2;
+  return host_form(
+      proc, pdu, grid, nof_ports, nof_subc, sizeof(srs_amd_pucch_uci_result), payload_stride,
+      [&](const Pdu& p) {
+        return slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
+                    proc->host_res.as<srs_amd_pucch_uci_result>(), proc->host_payload.as<uint8_t>(), payload_stride,
+                    proc->stream, llrs == nullptr);
+      },
+      [&](host_call& call, const Pdu& p) {
+        if (llrs != nullptr) {
+          call.out(llrs, proc->work.ptr, llr_len(p));
+        } else {
+          call.out(result, proc->host_res.ptr, sizeof(*result));
+          call.out(payload, proc->host_payload.ptr, K);
+        }
+      });
+}
+
+// Host forms of Format 2; the payload row is the PDU's own size when decoding (the slot form checks the stride
+// before the payload size).
+int f2_host(srs_amd_pucch_processor* proc, const srs_amd_pucch_f2_pdu* pdu, const uint32_t* grid, uint32_t nof_ports,
+            uint32_t nof_subc, srs_amd_pucch_uci_result* result, uint8_t* payload, int8_t* llrs)
+{
+  const uint32_t K = pdu != nullptr ? pdu->nof_harq_ack + pdu->nof_sr + pdu->nof_csi_part1 + pdu->nof_csi_part2 : 0u;
+  return uci_host(proc, pdu, grid, nof_ports, nof_subc, result, payload, llrs, llrs != nullptr ? 1706u : std::max(K, 1u),
+                  f2_slot, [](const srs_amd_pucch_f2_pdu& p) { return 16 * p.nof_prb * p.nof_symbols; });
+}
+
+// Host forms of Formats 3 / 4.
+int f34_host(srs_amd_pucch_processor* proc, const srs_amd_pucch_f34_pdu* pdu, const uint32_t* grid,
+             uint32_t nof_ports, uint32_t nof_subc, srs_amd_pucch_uci_result* result, uint8_t* payload, int8_t* llrs)
+{
+  return uci_host(proc, pdu, grid, nof_ports, nof_subc, result, payload, llrs, 1706u, f34_slot,
+                  [](const srs_amd_pucch_f34_pdu& p) {
+                    const bool     f4 = p.format == 4;
+                    const uint32_t nd = static_cast<uint32_t>(__builtin_popcount(
+                        f34_dmrs_mask(p.nof_symbols, p.second_hop_prb >= 0, p.additional_dmrs != 0)));
+                    return (p.nof_symbols - nd) * 12 * (f4 ? 1u : p.nof_prb) * (p.pi2_bpsk ? 1u : 2u) /
+                           (f4 ? p.occ_length : 1u);
+                  });
 }
 
 } // namespace
@@ -837,47 +1006,30 @@ int srs_amd_pucch_f0_detect_slot(srs_amd_pucch_processor*    proc,
                                  srs_amd_pucch_f0_result*    d_results,
                                  void*                       stream)
 {
-  if (proc == nullptr || (nof_pdus != 0 && (pdus == nullptr || d_results == nullptr))) {
-    return fail(SRS_AMD_EINVAL, "null argument");
-  }
-  if (nof_pdus == 0) {
-    return SRS_AMD_OK;
-  }
-  if (nof_subc == 0 || nof_subc % 12 != 0) {
-    return fail(SRS_AMD_EINVAL, "Invalid number of grid subcarriers (i.e., %u).", nof_subc);
+  int rc = SRS_AMD_OK;
+  if (!slot_entry(proc, nof_pdus, pdus != nullptr && d_results != nullptr, nof_subc, rc)) {
+    return rc;
   }
   std::lock_guard<std::mutex> lock(proc->mtx);
   std::vector<pucch_f0_desc>  desc(nof_pdus);
   for (uint32_t i = 0; i != nof_pdus; ++i) {
-    const int rc = make_desc(proc, pdus[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, desc[i]);
+    rc = make_desc(proc, pdus[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, desc[i]);
     if (rc != SRS_AMD_OK) {
       return rc;
     }
   }
   const size_t bytes = sizeof(pucch_f0_desc) * nof_pdus;
   auto         s     = static_cast<hipStream_t>(stream);
-  hipError_t   e     = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->buf.ensure(bytes);
+  staged_call  call("PUCCH processor", proc->device, proc->buf, bytes, proc->stage, bytes, proc->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e == hipSuccess) {
-    e = proc->stage.acquire(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH processor scratch");
-  }
-  call_scope scope(proc->order, nullptr, s);
-  std::memcpy(proc->stage.at<uint8_t>(0), desc.data(), bytes);
-  e = proc->stage.upload(proc->buf.ptr, bytes, s);
+  std::memcpy(call.host(), desc.data(), bytes);
+  hipError_t e = call.upload(proc->buf.ptr, bytes);
   if (e == hipSuccess) {
     e = launch_pucch_f0(proc->buf.as<pucch_f0_desc>(), nof_pdus, d_results, s);
   }
-  const int        rc   = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_f0_kernel launch");
-  const hipError_t done = scope.close();
-  return rc != SRS_AMD_OK ? rc : (done == hipSuccess ? SRS_AMD_OK : hip_fail(done, "PUCCH completion event"));
+  return call.finish(e);
 }
 
 int srs_amd_pucch_f0_detect(srs_amd_pucch_processor*    proc,
@@ -890,161 +1042,14 @@ int srs_amd_pucch_f0_detect(srs_amd_pucch_processor*    proc,
   if (proc == nullptr || pdu == nullptr || grid == nullptr || result == nullptr) {
     return fail(SRS_AMD_EINVAL, "null argument");
   }
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->host_res.ensure(sizeof(srs_amd_pucch_f0_result));
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH grid upload");
-  }
-  srs_amd_pucch_f0_pdu p = *pdu;
-  p.grid                 = 0;
-  p.d_grid               = nullptr;
-  int rc = srs_amd_pucch_f0_detect_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
-                                        proc->host_res.as<srs_amd_pucch_f0_result>(), proc->stream);
-  if (rc == SRS_AMD_OK) {
-    e  = hipMemcpyAsync(result, proc->host_res.ptr, sizeof(*result), hipMemcpyDeviceToHost, proc->stream);
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PUCCH result download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
-  }
-  return rc;
+  return host_form(
+      proc, pdu, grid, nof_ports, nof_subc, sizeof(srs_amd_pucch_f0_result), 0,
+      [&](const srs_amd_pucch_f0_pdu& p) {
+        return srs_amd_pucch_f0_detect_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
+                                            proc->host_res.as<srs_amd_pucch_f0_result>(), proc->stream);
+      },
+      [&](host_call& call, const srs_amd_pucch_f0_pdu&) { call.out(result, proc->host_res.ptr, sizeof(*result)); });
 }
-
-} // extern "C"
-
-namespace {
-
-// The Format 2 slot form; decode = false stops after the LLRs (rows of PUCCH_F2_MAX_E in proc->work, decoder order).
-int f2_slot(srs_amd_pucch_processor*    proc,
-            const srs_amd_pucch_f2_pdu* pdus,
-            uint32_t                    nof_pdus,
-            const uint32_t*             d_grids,
-            uint64_t                    grid_stride,
-            uint32_t                    nof_grids,
-            uint32_t                    nof_grid_ports,
-            uint32_t                    nof_subc,
-            srs_amd_pucch_uci_result*   d_results,
-            uint8_t*                    d_payloads,
-            uint64_t                    payload_stride,
-            void*                       stream,
-            bool                        decode)
-{
-  if (proc == nullptr || (nof_pdus != 0 && (pdus == nullptr || d_results == nullptr || d_payloads == nullptr))) {
-    return fail(SRS_AMD_EINVAL, "null argument");
-  }
-  if (nof_pdus == 0) {
-    return SRS_AMD_OK;
-  }
-  if (nof_subc == 0 || nof_subc % 12 != 0) {
-    return fail(SRS_AMD_EINVAL, "Invalid number of grid subcarriers (i.e., %u).", nof_subc);
-  }
-  std::lock_guard<std::mutex> lock(proc->mtx);
-  std::vector<pucch_f2_desc>  desc(nof_pdus);
-  std::vector<uint32_t>       K(nof_pdus), E(nof_pdus);
-  uint32_t                    max_k = 0;
-  for (uint32_t i = 0; i != nof_pdus; ++i) {
-    const srs_amd_pucch_f2_pdu& p = pdus[i];
-    if (p.nof_harq_ack + p.nof_sr + p.nof_csi_part1 + p.nof_csi_part2 > payload_stride) {
-      return fail(SRS_AMD_EINVAL, "payload_stride %llu below the PDU's %u payload bits.",
-                  static_cast<unsigned long long>(payload_stride),
-                  p.nof_harq_ack + p.nof_sr + p.nof_csi_part1 + p.nof_csi_part2);
-    }
-  }
-  // decoder order: PDUs grouped by (payload, codeword) size, one UCI decoder launch per group
-  std::vector<uint32_t> perm(nof_pdus);
-  for (uint32_t i = 0; i != nof_pdus; ++i) {
-    const srs_amd_pucch_f2_pdu& p = pdus[i];
-    K[i]  = p.nof_harq_ack + p.nof_sr + p.nof_csi_part1 + p.nof_csi_part2;
-    E[i]  = 16 * p.nof_prb * p.nof_symbols;
-    max_k = std::max(max_k, K[i]);
-  }
-  std::iota(perm.begin(), perm.end(), 0u);
-  std::stable_sort(perm.begin(), perm.end(),
-                   [&](uint32_t a, uint32_t b) { return K[a] != K[b] ? K[a] < K[b] : E[a] < E[b]; });
-  const uint32_t msg_stride = (std::max(max_k, 1u) + 63) / 64 * 64;
-  const size_t   llr_bytes  = static_cast<size_t>(nof_pdus) * PUCCH_F2_MAX_E;
-  const size_t   msg_bytes  = static_cast<size_t>(nof_pdus) * msg_stride;
-  const size_t   st_bytes   = static_cast<size_t>(nof_pdus) * sizeof(int32_t);
-  auto           s          = static_cast<hipStream_t>(stream);
-  hipError_t     e          = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->work.ensure(llr_bytes + msg_bytes + st_bytes);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH processor scratch");
-  }
-  int8_t*  d_llr = proc->work.as<int8_t>();
-  uint8_t* d_msg = proc->work.as<uint8_t>() + llr_bytes;
-  int32_t* d_st  = reinterpret_cast<int32_t*>(proc->work.as<uint8_t>() + llr_bytes + msg_bytes);
-  std::vector<uint32_t> nbits(nof_pdus);
-  for (uint32_t j = 0; j != nof_pdus; ++j) {
-    const uint32_t i = perm[j];
-    const int rc = make_f2_desc(proc, pdus[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, desc[j]);
-    if (rc != SRS_AMD_OK) {
-      return rc;
-    }
-    desc[j].llr    = d_llr + static_cast<size_t>(j) * PUCCH_F2_MAX_E;
-    desc[j].result = d_results + i;
-    nbits[j]       = K[i];
-  }
-  const size_t dbytes = sizeof(pucch_f2_desc) * nof_pdus;
-  const size_t ioff   = (dbytes + 255) & ~size_t(255);
-  const size_t ibytes = sizeof(uint32_t) * nof_pdus;
-  const size_t bytes  = ioff + 2 * ibytes;
-  if (e == hipSuccess) {
-    e = proc->buf.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->stage.acquire(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH processor scratch");
-  }
-  call_scope scope(proc->order, nullptr, s);
-  std::memcpy(proc->stage.at<uint8_t>(0), desc.data(), dbytes);
-  std::memcpy(proc->stage.at<uint8_t>(ioff), perm.data(), ibytes);
-  std::memcpy(proc->stage.at<uint8_t>(ioff + ibytes), nbits.data(), ibytes);
-  e = proc->stage.upload(proc->buf.ptr, bytes, s);
-  if (e == hipSuccess) {
-    e = launch_pucch_f2(proc->buf.as<pucch_f2_desc>(), nof_pdus, s);
-  }
-  int rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_f2_kernel launch");
-  for (uint32_t j0 = 0; decode && rc == SRS_AMD_OK && j0 != nof_pdus;) {
-    uint32_t j1 = j0 + 1;
-    while (j1 != nof_pdus && K[perm[j1]] == K[perm[j0]] && E[perm[j1]] == E[perm[j0]]) {
-      ++j1;
-    }
-    rc = srs_amd_uci_decode_batch(proc->uci, d_llr + static_cast<size_t>(j0) * PUCCH_F2_MAX_E, PUCCH_F2_MAX_E,
-                                  E[perm[j0]], K[perm[j0]], 2, d_msg + static_cast<size_t>(j0) * msg_stride,
-                                  msg_stride, d_st + j0, sizeof(int32_t), j1 - j0, s);
-    j0 = j1;
-  }
-  if (decode && rc == SRS_AMD_OK) {
-    const uint32_t* d_perm = reinterpret_cast<const uint32_t*>(proc->buf.as<uint8_t>() + ioff);
-    e  = launch_pucch_uci_finish(d_st, d_msg, msg_stride, d_perm, d_perm + nof_pdus, nof_pdus, d_results, d_payloads,
-                                 payload_stride, s);
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_uci_finish_kernel launch");
-  }
-  const hipError_t done = scope.close();
-  return rc != SRS_AMD_OK ? rc : (done == hipSuccess ? SRS_AMD_OK : hip_fail(done, "PUCCH completion event"));
-}
-
-} // namespace
-
-extern "C" {
 
 int srs_amd_pucch_f2_process_slot(srs_amd_pucch_processor*    proc,
                                   const srs_amd_pucch_f2_pdu* pdus,
@@ -1070,42 +1075,10 @@ int srs_amd_pucch_f2_demodulate(srs_amd_pucch_processor*    proc,
                                 uint32_t                    nof_subc,
                                 int8_t*                     llrs)
 {
-  if (proc == nullptr || pdu == nullptr || grid == nullptr || llrs == nullptr) {
+  if (llrs == nullptr) {
     return fail(SRS_AMD_EINVAL, "null argument");
   }
-  const uint32_t              E     = 16 * pdu->nof_prb * pdu->nof_symbols;
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->host_res.ensure(sizeof(srs_amd_pucch_uci_result));
-  }
-  if (e == hipSuccess) {
-    e = proc->host_payload.ensure(1706);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH grid upload");
-  }
-  srs_amd_pucch_f2_pdu p = *pdu;
-  p.grid                 = 0;
-  p.d_grid               = nullptr;
-  int rc = f2_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
-                   proc->host_res.as<srs_amd_pucch_uci_result>(), proc->host_payload.as<uint8_t>(), 1706,
-                   proc->stream, false);
-  if (rc == SRS_AMD_OK) {
-    e  = hipMemcpyAsync(llrs, proc->work.ptr, E, hipMemcpyDeviceToHost, proc->stream);
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PUCCH LLR download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
-  }
-  return rc;
+  return f2_host(proc, pdu, grid, nof_ports, nof_subc, nullptr, nullptr, llrs);
 }
 
 int srs_amd_pucch_f2_process(srs_amd_pucch_processor*    proc,
@@ -1116,45 +1089,10 @@ int srs_amd_pucch_f2_process(srs_amd_pucch_processor*    proc,
                              srs_amd_pucch_uci_result*   result,
                              uint8_t*                    payload)
 {
-  if (proc == nullptr || pdu == nullptr || grid == nullptr || result == nullptr || payload == nullptr) {
+  if (result == nullptr || payload == nullptr) {
     return fail(SRS_AMD_EINVAL, "null argument");
   }
-  const uint32_t              K     = pdu->nof_harq_ack + pdu->nof_sr + pdu->nof_csi_part1 + pdu->nof_csi_part2;
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->host_res.ensure(sizeof(srs_amd_pucch_uci_result));
-  }
-  if (e == hipSuccess) {
-    e = proc->host_payload.ensure(std::max(K, 1u));
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH grid upload");
-  }
-  srs_amd_pucch_f2_pdu p = *pdu;
-  p.grid                 = 0;
-  p.d_grid               = nullptr;
-  int rc = srs_amd_pucch_f2_process_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
-                                         proc->host_res.as<srs_amd_pucch_uci_result>(),
-                                         proc->host_payload.as<uint8_t>(), std::max(K, 1u), proc->stream);
-  if (rc == SRS_AMD_OK) {
-    e = hipMemcpyAsync(result, proc->host_res.ptr, sizeof(*result), hipMemcpyDeviceToHost, proc->stream);
-    if (e == hipSuccess && K != 0) {
-      e = hipMemcpyAsync(payload, proc->host_payload.ptr, K, hipMemcpyDeviceToHost, proc->stream);
-    }
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PUCCH result download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
-  }
-  return rc;
+  return f2_host(proc, pdu, grid, nof_ports, nof_subc, result, payload, nullptr);
 }
 
 int srs_amd_pucch_f34_process_slot(srs_amd_pucch_processor*     proc,
@@ -1173,64 +1111,6 @@ int srs_amd_pucch_f34_process_slot(srs_amd_pucch_processor*     proc,
   return f34_slot(proc, pdus, nof_pdus, d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc, d_results,
                   d_payloads, payload_stride, stream, true);
 }
-
-namespace {
-
-// Host forms of Formats 3 / 4: the grid up, one PDU, the result and payload (or the LLRs) down.
-int f34_host(srs_amd_pucch_processor* proc, const srs_amd_pucch_f34_pdu* pdu, const uint32_t* grid,
-             uint32_t nof_ports, uint32_t nof_subc, srs_amd_pucch_uci_result* result, uint8_t* payload, int8_t* llrs)
-{
-  if (proc == nullptr || pdu == nullptr || grid == nullptr || (llrs == nullptr && (result == nullptr || payload == nullptr))) {
-    return fail(SRS_AMD_EINVAL, "null argument");
-  }
-  const uint32_t              K     = pdu->nof_harq_ack + pdu->nof_sr + pdu->nof_csi_part1 + pdu->nof_csi_part2;
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->host_res.ensure(sizeof(srs_amd_pucch_uci_result));
-  }
-  if (e == hipSuccess) {
-    e = proc->host_payload.ensure(1706);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH grid upload");
-  }
-  srs_amd_pucch_f34_pdu p = *pdu;
-  p.grid                  = 0;
-  p.d_grid                = nullptr;
-  int rc = f34_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
-                    proc->host_res.as<srs_amd_pucch_uci_result>(), proc->host_payload.as<uint8_t>(), 1706,
-                    proc->stream, llrs == nullptr);
-  if (rc == SRS_AMD_OK) {
-    if (llrs != nullptr) {
-      const bool     f4  = p.format == 4;
-      const uint32_t nd  = static_cast<uint32_t>(__builtin_popcount(f34_dmrs_mask(p.nof_symbols, p.second_hop_prb >= 0,
-                                                                                  p.additional_dmrs != 0)));
-      const uint32_t E   = (p.nof_symbols - nd) * 12 * (f4 ? 1u : p.nof_prb) * (p.pi2_bpsk ? 1u : 2u) /
-                         (f4 ? p.occ_length : 1u);
-      e = hipMemcpyAsync(llrs, proc->work.ptr, E, hipMemcpyDeviceToHost, proc->stream);
-    } else {
-      e = hipMemcpyAsync(result, proc->host_res.ptr, sizeof(*result), hipMemcpyDeviceToHost, proc->stream);
-      if (e == hipSuccess && K != 0) {
-        e = hipMemcpyAsync(payload, proc->host_payload.ptr, K, hipMemcpyDeviceToHost, proc->stream);
-      }
-    }
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PUCCH result download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
-  }
-  return rc;
-}
-
-} // namespace
 
 int srs_amd_pucch_f34_process(srs_amd_pucch_processor*     proc,
                               const srs_amd_pucch_f34_pdu* pdu,
@@ -1270,21 +1150,16 @@ int srs_amd_pucch_f1_detect_slot(srs_amd_pucch_processor*      proc,
                                  srs_amd_pucch_result*         d_results,
                                  void*                         stream)
 {
-  if (proc == nullptr || (nof_batches != 0 && (batches == nullptr || d_results == nullptr))) {
-    return fail(SRS_AMD_EINVAL, "null argument");
-  }
-  if (nof_batches == 0) {
-    return SRS_AMD_OK;
-  }
-  if (nof_subc == 0 || nof_subc % 12 != 0) {
-    return fail(SRS_AMD_EINVAL, "Invalid number of grid subcarriers (i.e., %u).", nof_subc);
+  int rc = SRS_AMD_OK;
+  if (!slot_entry(proc, nof_batches, batches != nullptr && d_results != nullptr, nof_subc, rc)) {
+    return rc;
   }
   std::lock_guard<std::mutex>         lock(proc->mtx);
   std::vector<pucch_f1_desc>          desc(nof_batches);
   std::vector<srs_amd_pucch_f1_entry> ent;
   for (uint32_t i = 0; i != nof_batches; ++i) {
-    const int rc = make_f1_desc(proc, batches[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc,
-                                static_cast<uint32_t>(ent.size()), desc[i]);
+    rc = make_f1_desc(proc, batches[i], d_grids, grid_stride, nof_grids, nof_grid_ports, nof_subc,
+                      static_cast<uint32_t>(ent.size()), desc[i]);
     if (rc != SRS_AMD_OK) {
       return rc;
     }
@@ -1295,33 +1170,18 @@ int srs_amd_pucch_f1_detect_slot(srs_amd_pucch_processor*      proc,
   const size_t eoff   = (dbytes + 255) & ~size_t(255);
   const size_t bytes  = eoff + ebytes;
   auto         s      = static_cast<hipStream_t>(stream);
-  hipError_t   e      = hipSetDevice(proc->device);
+  staged_call  call("PUCCH processor", proc->device, proc->buf, bytes, proc->stage, bytes, proc->order, s);
+  if (!call.ok()) {
+    return call.finish();
+  }
+  std::memcpy(call.host(), desc.data(), dbytes);
+  std::memcpy(call.host(eoff), ent.data(), ebytes);
+  hipError_t e = call.upload(proc->buf.ptr, bytes);
   if (e == hipSuccess) {
-    e = proc->buf.ensure(bytes);
+    e = launch_pucch_f1(proc->buf.as<pucch_f1_desc>(), nof_batches,
+                        reinterpret_cast<const srs_amd_pucch_f1_entry*>(proc->buf.as<uint8_t>() + eoff), d_results, s);
   }
-  if (e == hipSuccess) {
-    e = proc->stage.acquire(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH processor scratch");
-  }
-  call_scope scope(proc->order, nullptr, s);
-  std::memcpy(proc->stage.at<uint8_t>(0), desc.data(), dbytes);
-  std::memcpy(proc->stage.at<uint8_t>(eoff), ent.data(), ebytes);
-  e = proc->stage.upload(proc->buf.ptr, bytes, s);
-  if (e == hipSuccess) {
-    e = launch_pucch_f1(proc->buf.as<pucch_f1_desc>(),
-                        nof_batches,
-                        reinterpret_cast<const srs_amd_pucch_f1_entry*>(proc->buf.as<uint8_t>() + eoff),
-                        d_results,
-                        s);
-  }
-  const int        rc   = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pucch_f1_kernel launch");
-  const hipError_t done = scope.close();
-  return rc != SRS_AMD_OK ? rc : (done == hipSuccess ? SRS_AMD_OK : hip_fail(done, "PUCCH completion event"));
+  return call.finish(e);
 }
 
 int srs_amd_pucch_f1_detect(srs_amd_pucch_processor*      proc,
@@ -1337,35 +1197,14 @@ int srs_amd_pucch_f1_detect(srs_amd_pucch_processor*      proc,
   if (batch->nof_entries == 0 || batch->nof_entries > PUCCH_F1_MAX_ENTRIES) {
     return fail(SRS_AMD_EINVAL, "Invalid number of multiplexed PUCCH (i.e., %u).", batch->nof_entries);
   }
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  const size_t                rbytes = sizeof(srs_amd_pucch_result) * batch->nof_entries;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e == hipSuccess) {
-    e = proc->host_res.ensure(rbytes);
-  }
-  if (e == hipSuccess) {
-    e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUCCH grid upload");
-  }
-  srs_amd_pucch_f1_batch b = *batch;
-  b.grid                   = 0;
-  b.d_grid                 = nullptr;
-  int rc = srs_amd_pucch_f1_detect_slot(proc, &b, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
-                                        proc->host_res.as<srs_amd_pucch_result>(), proc->stream);
-  if (rc == SRS_AMD_OK) {
-    e  = hipMemcpyAsync(results, proc->host_res.ptr, rbytes, hipMemcpyDeviceToHost, proc->stream);
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "PUCCH result download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
-  }
-  return rc;
+  const size_t rbytes = sizeof(srs_amd_pucch_result) * batch->nof_entries;
+  return host_form(
+      proc, batch, grid, nof_ports, nof_subc, rbytes, 0,
+      [&](const srs_amd_pucch_f1_batch& b) {
+        return srs_amd_pucch_f1_detect_slot(proc, &b, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
+                                            proc->host_res.as<srs_amd_pucch_result>(), proc->stream);
+      },
+      [&](host_call& call, const srs_amd_pucch_f1_batch&) { call.out(results, proc->host_res.ptr, rbytes); });
 }
 
 } // extern "C"

@@ -18,6 +18,7 @@
 #include "gold_sequence.h"
 #include "modulation_args.h"
 #include "pusch_demod_args.h"
+#include "staged_call.h"
 #include "srsran_amd/modulation.h"
 #include <algorithm>
 #include <cstring>
@@ -321,33 +322,28 @@ int srs_amd::pusch_demodulate_slot_fused(::srs_amd_pusch_demodulator* dem,
   auto         s     = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lock(dem->mtx);
   hipError_t                  e = hipSetDevice(dem->device);
-  if (e == hipSuccess) {
-    e = dem->slot_items.ensure(total);
-  }
   if (e == hipSuccess && tp_res != 0) {
     e = dem->scratch.ensure(tp_res * (sizeof(float2) + sizeof(float)));
   }
+  if (e != hipSuccess) {
+    return hip_fail(e, "PUSCH demodulator slot scratch");
+  }
   float2* const eq_out = dem->scratch.as<float2>();
   float* const  nv_out = reinterpret_cast<float*>(eq_out + tp_res);
-  for (uint32_t i = 0; i != nof_items && e == hipSuccess; ++i) {
+  for (uint32_t i = 0; i != nof_items; ++i) {
     if (items[i].plan->tp_subc != 0) {
       pairs[i].a.eq_out    = eq_out + tp_off[i];
       pairs[i].a.nv_out    = nv_out + tp_off[i];
       pairs[i].a.eq_stride = items[i].plan->args.nof_re;
     }
   }
-  if (e == hipSuccess) {
-    e = dem->stage.acquire(total);
+  staged_call call("PUSCH demodulator slot", staged_call::DEVICE_IS_CURRENT, dem->slot_items, total, dem->stage, total,
+                   dem->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e == hipSuccess) {
-    e = dem->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "PUSCH demodulator slot descriptors");
-  }
-  call_scope scope(dem->order, nullptr, s);
-  std::memcpy(dem->stage.at<eq_item>(0), pairs.data(), sizeof(eq_item) * nof_items);
-  std::memcpy(dem->stage.at<uint32_t>(o_ids), order.data(), sizeof(uint32_t) * order.size());
+  std::memcpy(call.host(), pairs.data(), sizeof(eq_item) * nof_items);
+  std::memcpy(call.host(o_ids), order.data(), sizeof(uint32_t) * order.size());
   // transform-precoded PDUs: deprecoder rows and demapper of each (one launch each for all of them)
   uint32_t tp_rows = 0, tp_syms = 0;
   size_t   tp_lds  = 0;
@@ -369,15 +365,15 @@ int srs_amd::pusch_demodulate_slot_fused(::srs_amd_pusch_demodulator* dem,
     if (rc != SRS_AMD_OK) {
       return rc;
     }
-    std::memcpy(dem->stage.at<tp_args>(o_tp + sizeof(tp_args) * k), &ta, sizeof(ta));
-    std::memcpy(dem->stage.at<demap_item>(o_dm + sizeof(demap_item) * k), &di, sizeof(di));
+    std::memcpy(call.host(o_tp + sizeof(tp_args) * k), &ta, sizeof(ta));
+    std::memcpy(call.host(o_dm + sizeof(demap_item) * k), &di, sizeof(di));
     tp_rows = std::max(tp_rows, ta.nof_rows);
     tp_syms = std::max(tp_syms, pl->args.nof_re);
     tp_lds  = std::max(tp_lds, lds);
     ++k;
   }
   auto* d = dem->slot_items.as<uint8_t>();
-  e       = dem->stage.upload(d, total, s);
+  e       = call.upload(d, total);
   for (const group& g : groups) {
     if (e != hipSuccess) {
       break;
@@ -393,10 +389,9 @@ int srs_amd::pusch_demodulate_slot_fused(::srs_amd_pusch_demodulator* dem,
     e = launch_demap_descramble_items(reinterpret_cast<const demap_item*>(d + o_dm), static_cast<uint32_t>(n_tp),
                                       tp_syms, s);
   }
-  const hipError_t done = scope.close();
-  e                     = e != hipSuccess ? e : done;
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "pusch_equalize_fused_kernel slot launch");
+  return call.finish(e);
 }
+
 
 extern "C" {
 

@@ -12,6 +12,7 @@
 #include "device_buffer.h"
 #include "dft_engine.h"
 #include "srs_args.h"
+#include "staged_call.h"
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -216,6 +217,7 @@ struct srs_amd_srs_estimator {
   pinned_stage                stage;
   stream_order                order;
   std::mutex                  mtx;
+  std::mutex                  host_mtx; // the host form's buffer and stream
 
   ~srs_amd_srs_estimator()
   {
@@ -409,10 +411,7 @@ int srs_amd_srs_estimate_batch(srs_amd_srs_estimator*    est,
     return hip_fail(e, "SRS estimator device");
   }
   const size_t bytes = static_cast<size_t>(nof_pdus) * sizeof(srs_pdu);
-  e                  = est->descriptors.ensure(bytes);
-  if (e == hipSuccess) {
-    e = est->partials.ensure(static_cast<size_t>(nof_pdus) * sizeof(srs_partial));
-  }
+  e                  = est->partials.ensure(static_cast<size_t>(nof_pdus) * sizeof(srs_partial));
   if (e != hipSuccess) {
     return hip_fail(e, "SRS estimator scratch");
   }
@@ -453,16 +452,13 @@ int srs_amd_srs_estimate_batch(srs_amd_srs_estimator*    est,
     o.ta_resolution_s = 1.0 / g.sampling_rate;
     o.ta_max_s        = static_cast<double>(g.max_ta_samples) / g.sampling_rate;
   }
-  e = est->stage.acquire(bytes);
-  if (e == hipSuccess) {
-    e = est->order.begin(s);
+  staged_call call("SRS estimator", staged_call::DEVICE_IS_CURRENT, est->descriptors, bytes, est->stage, bytes,
+                   est->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e != hipSuccess) {
-    return hip_fail(e, "SRS estimator scratch");
-  }
-  call_scope scope(est->order, nullptr, s);
-  std::memcpy(est->stage.at<uint8_t>(0), pdus.data(), bytes);
-  e                    = est->stage.upload(est->descriptors.ptr, bytes, s);
+  std::memcpy(call.host(), pdus.data(), bytes);
+  e                    = call.upload(est->descriptors.ptr, bytes);
   const srs_pdu* d_pdu = est->descriptors.as<srs_pdu>();
   for (uint32_t k = 0; k != NOF_IDFT_SIZES && e == hipSuccess; ++k) {
     e = launch_srs_ta(d_pdu + group_begin[k], group_begin[k + 1] - group_begin[k], IDFT_SIZES[k], s);
@@ -473,12 +469,7 @@ int srs_amd_srs_estimate_batch(srs_amd_srs_estimator*    est,
   if (e == hipSuccess) {
     e = launch_srs_finish(d_pdu, nof_pdus, s);
   }
-  const int        rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "SRS estimator launch");
-  const hipError_t ce = scope.close();
-  if (rc == SRS_AMD_OK && ce != hipSuccess) {
-    return hip_fail(ce, "SRS estimator completion event");
-  }
-  return rc;
+  return call.finish(e);
 }
 
 int srs_amd_srs_estimate(srs_amd_srs_estimator*    est,
@@ -498,33 +489,22 @@ int srs_amd_srs_estimate(srs_amd_srs_estimator*    est,
   }
   const size_t in_bytes = static_cast<size_t>(nof_ports) * SRS_NSYMB * nof_subc * sizeof(uint32_t);
   const size_t res_off  = align_up(in_bytes, 16);
-  hipError_t   e        = hipSuccess;
-  {
-    std::lock_guard<std::mutex> lock(est->mtx);
-    e = hipSetDevice(est->device);
-    if (e == hipSuccess) {
-      e = est->host_io.ensure(res_off + sizeof(srs_amd_srs_result));
-    }
-    if (e == hipSuccess) {
-      e = hipMemcpyAsync(est->host_io.ptr, grid, in_bytes, hipMemcpyHostToDevice, est->stream);
-    }
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "SRS estimator upload");
+  host_call    call("SRS estimator", est->host_mtx, est->device, est->stream);
+  call.grow(est->host_io, res_off + sizeof(srs_amd_srs_result));
+  call.in(est->host_io.ptr, grid, in_bytes);
+  if (!call.ok()) {
+    return call.finish();
   }
   auto*              d_res = reinterpret_cast<srs_amd_srs_result*>(est->host_io.as<uint8_t>() + res_off);
   srs_amd_srs_config c     = *config;
   c.grid                   = 0;
   c.d_grid                 = nullptr;
   rc = srs_amd_srs_estimate_batch(est, &c, 1, est->host_io.as<uint32_t>(), 0, 1, nof_ports, nof_subc, d_res, est->stream);
-  if (rc != SRS_AMD_OK) {
-    return rc;
+  if (rc == SRS_AMD_OK) {
+    call.out(result, d_res, sizeof(srs_amd_srs_result));
   }
-  e = hipMemcpyAsync(result, d_res, sizeof(srs_amd_srs_result), hipMemcpyDeviceToHost, est->stream);
-  if (e == hipSuccess) {
-    e = hipStreamSynchronize(est->stream);
-  }
-  return e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "SRS estimator download");
+  return call.finish(rc);
 }
+
 
 } // extern "C"

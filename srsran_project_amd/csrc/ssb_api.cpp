@@ -12,6 +12,7 @@
 #include "device_buffer.h"
 #include "gold_sequence.h"
 #include "ssb_args.h"
+#include "staged_call.h"
 #include <array>
 #include <cmath>
 #include <cstring>
@@ -315,37 +316,25 @@ int srs_amd_ssb_process_slot(srs_amd_ssb_processor* proc,
   const size_t total  = o_cw + align_up(static_cast<size_t>(SSB_E) * nof_pdus, 256);
   const size_t staged = sizeof(ssb_desc) * nof_pdus;
   auto         s      = static_cast<hipStream_t>(stream);
-  hipError_t   e      = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->buf.ensure(total);
+  staged_call  call("SSB processor", proc->device, proc->buf, total, proc->stage, staged, proc->order, s);
+  if (!call.ok()) {
+    return call.finish();
   }
-  if (e == hipSuccess) {
-    e = proc->stage.acquire(staged);
-  }
-  if (e == hipSuccess) {
-    e = proc->order.begin(s);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "SSB processor scratch");
-  }
-  call_scope scope(proc->order, nullptr, s);
-  std::memcpy(proc->stage.at<uint8_t>(0), desc.data(), staged);
-  auto* base   = proc->buf.as<uint8_t>();
-  auto* d_desc = reinterpret_cast<const ssb_desc*>(base);
-  e            = proc->stage.upload(base, staged, s);
+  std::memcpy(call.host(), desc.data(), staged);
+  auto*      base   = proc->buf.as<uint8_t>();
+  auto*      d_desc = reinterpret_cast<const ssb_desc*>(base);
+  hipError_t e      = call.upload(base, staged);
   if (e == hipSuccess) {
     e = launch_ssb_encode(d_desc, nof_pdus, base + o_msg, proc->d_jump, s);
   }
-  int rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "ssb_encode_kernel launch");
-  if (rc == SRS_AMD_OK) {
+  int rc = SRS_AMD_OK;
+  if (e == hipSuccess) {
     rc = srs_amd_polar_encode_batch(proc->code, base + o_msg, SSB_K, base + o_cw, SSB_E, nof_pdus, stream);
   }
-  if (rc == SRS_AMD_OK) {
-    e  = launch_ssb_map(d_desc, nof_pdus, base + o_cw, proc->d_seq, proc->d_jump, s);
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "ssb_map_kernel launch");
+  if (e == hipSuccess && rc == SRS_AMD_OK) {
+    e = launch_ssb_map(d_desc, nof_pdus, base + o_cw, proc->d_seq, proc->d_jump, s);
   }
-  const hipError_t done = scope.close();
-  return rc != SRS_AMD_OK ? rc : (done == hipSuccess ? SRS_AMD_OK : hip_fail(done, "SSB completion event"));
+  return call.finish(e, rc);
 }
 
 int srs_amd_ssb_process(srs_amd_ssb_processor* proc,
@@ -357,32 +346,23 @@ int srs_amd_ssb_process(srs_amd_ssb_processor* proc,
   if (proc == nullptr || pdu == nullptr || grid == nullptr) {
     return fail(SRS_AMD_EINVAL, "null argument");
   }
-  const size_t                bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
-  std::lock_guard<std::mutex> host_lock(proc->host_mtx);
-  hipError_t                  e = hipSetDevice(proc->device);
-  if (e == hipSuccess) {
-    e = proc->host_grid.ensure(bytes);
-  }
-  if (e != hipSuccess) {
-    return hip_fail(e, "SSB processor grid");
-  }
-  e = hipMemcpyAsync(proc->host_grid.ptr, grid, bytes, hipMemcpyHostToDevice, proc->stream);
-  if (e != hipSuccess) {
-    return hip_fail(e, "SSB grid upload");
+  const size_t bytes = sizeof(uint32_t) * nof_ports * NSYMB * nof_subc;
+  host_call    call("SSB processor", proc->host_mtx, proc->device, proc->stream);
+  call.grow(proc->host_grid, bytes);
+  call.in(proc->host_grid.ptr, grid, bytes);
+  if (!call.ok()) {
+    return call.finish();
   }
   srs_amd_ssb_pdu p = *pdu;
   p.grid            = 0;
   p.d_grid          = nullptr;
-  int rc = srs_amd_ssb_process_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
-                                    proc->stream);
+  const int rc = srs_amd_ssb_process_slot(proc, &p, 1, proc->host_grid.as<uint32_t>(), 0, 1, nof_ports, nof_subc,
+                                          proc->stream);
   if (rc == SRS_AMD_OK) {
-    e  = hipMemcpyAsync(grid, proc->host_grid.ptr, bytes, hipMemcpyDeviceToHost, proc->stream);
-    e  = e == hipSuccess ? hipStreamSynchronize(proc->stream) : e;
-    rc = e == hipSuccess ? SRS_AMD_OK : hip_fail(e, "SSB grid download");
-  } else {
-    (void)hipStreamSynchronize(proc->stream);
+    call.out(grid, proc->host_grid.ptr, bytes);
   }
-  return rc;
+  return call.finish(rc);
 }
+
 
 } // extern "C"

@@ -246,3 +246,15 @@ def test_pdsch_reserves_the_csi_rs_res(gen, device):
     assert not np.array_equal(pdsch_only, unreserved)
     assert (unreserved[mask] != garbage[0][mask]).any()
     mod.close()
+
+
+def test_host_form_threads_on_one_handle_keep_their_own_input(gen):
+    """Four threads in the host form of ONE generator, each with its own scrambling identity and garbage grid on the
+    smallest fixture's resource (tests/host_form_threads.py): every call returns its own thread's grid bit for bit."""
+    from tests.host_form_threads import check_isolation
+
+    fx = min(FIXTURES, key=lambda f: (len(f.cfgs), f.nof_grid_ports, f.cfgs[0].nof_rb, f.nof_subc))
+    assert fx.name == "row1_one_prb"
+    inputs = [(cm.garbage_grid(1, fx.nof_grid_ports, fx.nof_subc, 7000 + i)[0],
+               fx.cfgs[0].library(scrambling_id=(fx.cfgs[0].scrambling_id + 1 + 97 * i) % 1024)) for i in range(4)]
+    check_isolation(lambda x: gen.map(x[0], x[1]), inputs, lambda grid: grid.tobytes())

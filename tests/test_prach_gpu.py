@@ -311,3 +311,25 @@ def test_invalid_configuration_launches_nothing(detector, device):
             detector.detect(fx.x, _config(fx, **bad))
     torch.cuda.synchronize()
     assert bool((results == 0xA5).all())  # the valid first occasion was not launched either
+
+
+def test_host_form_threads_on_one_handle_keep_their_own_input(detector):
+    """Four threads in the host form of ONE detector, each with its own seeded occasion of the smallest fixture's
+    configuration (tests/host_form_threads.py): every call returns its own thread's result bit for bit."""
+    import struct
+
+    from tests.host_form_threads import check_isolation
+
+    fx = min(FIXTURES, key=lambda f: np.asarray(f.x).size)
+    assert fx.name == "c0_15khz_zcz9_1port"
+    cfg = _config(fx)
+    occasions = [pm.make_occasion(np.random.default_rng(7000 + i), fx.format, fx.ra_scs, fx.zcz,
+                                  fx.root_sequence_index, fx.ports, fx.tx, 1.0, fx.idft_size) for i in range(4)]
+
+    def bits(r):
+        pre = b"".join(struct.pack("2i3d", p.preamble_index, p.delay_samples, p.time_advance_s, p.detection_metric,
+                                   p.preamble_power_db) for p in r.preambles)
+        return (struct.pack("3d", r.rssi_db, r.time_resolution_s, r.time_advance_max_s) + pre +
+                r.peak_over_threshold.tobytes() + r.delay_samples.tobytes())
+
+    check_isolation(lambda x: detector.detect(x, cfg), occasions, bits)

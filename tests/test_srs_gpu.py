@@ -334,3 +334,23 @@ def test_invalid_configuration_launches_nothing(estimator, device):
                 estimator.estimate(grid, fx.cfg.library(**bad))
     torch.cuda.synchronize()
     assert bool((results == 0xA5).all())  # the valid first PDU was not launched either
+
+
+def test_host_form_threads_on_one_handle_keep_their_own_input(estimator):
+    """Four threads in the host form of ONE estimator, each with its own reception of the smallest fixture's PDU
+    (tests/host_form_threads.py): every call returns its own thread's result bit for bit."""
+    import struct
+
+    from tests.host_form_threads import check_isolation
+
+    fx = min(FIXTURES, key=lambda f: f.x.size)
+    assert fx.name == "m12_comb4_1x1"
+    cfg = fx.cfg.library()
+    grids = [sm.build_grid(sm.make_rows(np.random.default_rng(7000 + i), fx.cfg, fx.nof_subc, 0.1 * (i + 1), 0.3),
+                           fx.cfg, max(fx.cfg.rx_ports) + 1, 7100 + i) for i in range(4)]
+
+    def bits(r):
+        return r.channel_matrix.tobytes() + struct.pack("7d", r.epre_db, r.rsrp_db, r.noise_variance,
+                                                        r.time_alignment_s, r.ta_resolution_s, r.ta_min_s, r.ta_max_s)
+
+    check_isolation(lambda g: estimator.estimate(g, cfg), grids, bits)
