@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void modulate_kernel(modulate_args a)
 
 __global__ __launch_bounds__(256) void demodulate_kernel(demodulate_args a)
 {
-  __shared__ float lt[4 * 2 * 16];
+  __shared__ alignas(16) float lt[LT_FLOATS];
   stage_interval_tables(a, lt);
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.nof_symbols) {
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void demap_descramble_kernel(demodulate_args o
   }
   __shared__ int8_t   s_llr[DD_SYMS * 8];
   __shared__ uint32_t words[DD_SYMS * 8 / 32];
-  __shared__ float    lt[4 * 2 * 16];
+  __shared__ alignas(16) float lt[LT_FLOATS];
   stage_interval_tables(a, lt);
   const uint32_t      g   = MULTI ? 0u : blockIdx.y;
   const uint32_t      bpp = a.qm < 1 ? 1u : static_cast<uint32_t>(a.qm); // LLRs per symbol

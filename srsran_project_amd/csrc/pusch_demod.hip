@@ -30,7 +30,21 @@ namespace {
 // Soft demapping and descrambling of the L x QM LLRs of data RE j (codeword symbols i = j L + layer) into
 // the grid's LLR row: demap_device.h's demapper (the SIMD or scalar arithmetic by the symbol's place in its
 // OFDM symbol, as the reference's per-OFDM-symbol demapper calls), the sign flipped where the Gold sequence
-// bit is one (the RE's L QM <= 32 sequence bits from two table words).
+// bit is one (the RE's L QM <= 32 sequence bits from two table words) inside the demapper
+// (demap_symbol_scrambled), the low bytes of the quantized values gathered with v_perm_b32.
+
+// low bytes of a (byte 0) and b (byte 1), the upper half zero
+__device__ __forceinline__ uint32_t pack_2(int a, int b)
+{
+  return __builtin_amdgcn_perm(static_cast<uint32_t>(b), static_cast<uint32_t>(a), 0x0c0c0400u);
+}
+
+// low bytes of a, b, c, d in bytes 0 .. 3
+__device__ __forceinline__ uint32_t pack_4(int a, int b, int c, int d)
+{
+  return __builtin_amdgcn_perm(pack_2(c, d), pack_2(a, b), 0x05040100u);
+}
+
 template <int L, int QM>
 __device__ __forceinline__ void emit_re_llrs(const pusch_eq_args& a, const float* lt, int8_t* row, uint32_t j,
                                              uint32_t simd_hi, const float2 (&s)[L], const float (&nv)[L])
@@ -41,29 +55,23 @@ __device__ __forceinline__ void emit_re_llrs(const pusch_eq_args& a, const float
 #pragma unroll
   for (int v = 0; v < L; ++v) {
     const uint32_t i = j * L + v;
-    int8_t         o[8];
-    demap::demap_symbol(a.dm, lt, s[v], nv[v], i, i < simd_hi, o);
-    const uint32_t c = cw >> (v * QM);
-    uint64_t       x = 0;
-#pragma unroll
-    for (int k = 0; k < QM; ++k) {
-      const int q = ((c >> k) & 1u) ? -o[k] : o[k];
-      x |= static_cast<uint64_t>(static_cast<uint8_t>(q)) << (8 * k);
-    }
+    int            q[8];
+    demap::demap_symbol_scrambled<QM>(a.dm, lt, s[v], nv[v], i, i < simd_hi, cw >> (v * QM), q);
     int8_t* dst = row + i * QM;
     if constexpr (QM == 8) {
-      *reinterpret_cast<uint2*>(dst) = make_uint2(static_cast<uint32_t>(x), static_cast<uint32_t>(x >> 32));
+      *reinterpret_cast<uint2*>(dst) = make_uint2(pack_4(q[0], q[1], q[2], q[3]), pack_4(q[4], q[5], q[6], q[7]));
     } else if constexpr (QM == 6) {
-      uint16_t* d16 = reinterpret_cast<uint16_t*>(dst); // i * 6 is even
-      d16[0]        = static_cast<uint16_t>(x);
-      d16[1]        = static_cast<uint16_t>(x >> 16);
-      d16[2]        = static_cast<uint16_t>(x >> 32);
+      uint16_t*      d16 = reinterpret_cast<uint16_t*>(dst); // i * 6 is even
+      const uint32_t x   = pack_4(q[0], q[1], q[2], q[3]);
+      d16[0]             = static_cast<uint16_t>(x);
+      d16[1]             = static_cast<uint16_t>(x >> 16);
+      d16[2]             = static_cast<uint16_t>(pack_2(q[4], q[5]));
     } else if constexpr (QM == 4) {
-      *reinterpret_cast<uint32_t*>(dst) = static_cast<uint32_t>(x);
+      *reinterpret_cast<uint32_t*>(dst) = pack_4(q[0], q[1], q[2], q[3]);
     } else if constexpr (QM == 2) {
-      *reinterpret_cast<uint16_t*>(dst) = static_cast<uint16_t>(x);
+      *reinterpret_cast<uint16_t*>(dst) = static_cast<uint16_t>(pack_2(q[0], q[1]));
     } else {
-      *dst = static_cast<int8_t>(x);
+      *dst = static_cast<int8_t>(q[0]);
     }
   }
 }
@@ -177,7 +185,7 @@ __device__ __forceinline__ void equalize_write(const pusch_eq_args& a, const flo
 template <int P, int L, bool MMSE>
 __global__ __launch_bounds__(256) void pusch_equalize_kernel(pusch_eq_args a)
 {
-  __shared__ float lt[4 * 2 * 16];
+  __shared__ alignas(16) float lt[demap::LT_FLOATS];
   demap::stage_interval_tables(a.dm, lt);
   const uint32_t  l   = a.first_symbol + blockIdx.y;
   const uint32_t  sc  = a.first_subc + blockIdx.x * 256 + threadIdx.x;
@@ -236,7 +244,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void p
   const chest_args&    c  = it.c;
   __shared__ float2 s_ph[P];
   __shared__ int    s_rot[P];
-  __shared__ float  lt[4 * 2 * 16];
+  __shared__ alignas(16) float lt[demap::LT_FLOATS];
   // XCD-aware order: workgroups are dispatched to the 8 XCDs round-robin, so the symbols of one (grid,
   // subcarrier tile) are placed on one XCD -- its L2 then serves their common LSE slices.
   const uint32_t xcd  = blockIdx.x % EQ_XCDS, r = blockIdx.x / EQ_XCDS;
@@ -269,13 +277,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void p
   const int       i0    = chdev::lse_index(c, l);
   const bool      two   = c.td != SRS_AMD_CHEST_TD_AVERAGE && c.td_interp[l];
   const bool      dc    = sc == a.dc_subc; // the processor's zeroed DC estimate (pusch_processor_impl.cpp:235-249)
-  // channel coefficient of port p, layer v
-  auto coef = [&](int p, int v) {
-    const float2*  fr = c.freq + (((static_cast<uint64_t>(gi) * P + p) * L + v) * c.nof_lse + i0) * c.nof_re + kk;
-    const float2   x0 = fr[0];
-    const float2   x1 = two ? fr[c.nof_re] : x0;
-    const uint32_t u  = chdev::expand_pair(c, x0, x1, l, s_rot[p] != 0, s_ph[p]);
-    return eq::from_cbf16(dc ? 0u : u);
+  // The channel coefficients of port p, layers 0 .. L - 1.  A (port, layer) slice starts a wave-uniform distance
+  // from the grid's first (a scalar base per slice); the thread's own part is one 32-bit byte offset (kk < nof_re).
+  // The L loads of a port are issued together, ahead of the rounding and rotation of the first.
+  const uint64_t fr_pv  = static_cast<uint64_t>(c.nof_lse) * c.nof_re * sizeof(float2);
+  const char*    fr0    = reinterpret_cast<const char*>(c.freq + i0 * c.nof_re) + gi * (P * L) * fr_pv;
+  const uint32_t fr_off = kk * static_cast<uint32_t>(sizeof(float2));
+  auto coefs = [&](int p, eq::cplx* hp) {
+    const char* fr = fr0 + (p * L) * fr_pv + fr_off;
+    float2      x0[L], x1[L];
+#pragma unroll
+    for (int v = 0; v < L; ++v) {
+      x0[v] = *reinterpret_cast<const float2*>(fr + v * fr_pv);
+    }
+    if (two) { // (a branch of its own: no second load, nor a select between two addresses, where one slice is read)
+#pragma unroll
+      for (int v = 0; v < L; ++v) {
+        x1[v] = *reinterpret_cast<const float2*>(fr + v * fr_pv + c.nof_re * sizeof(float2));
+      }
+#pragma unroll
+      for (int v = 0; v < L; ++v) {
+        hp[v] = eq::from_cbf16(dc ? 0u : chdev::expand_pair(c, x0[v], x1[v], l, s_rot[p] != 0, s_ph[p]));
+      }
+    } else {
+#pragma unroll
+      for (int v = 0; v < L; ++v) {
+        hp[v] = eq::from_cbf16(dc ? 0u : chdev::expand_pair(c, x0[v], x0[v], l, s_rot[p] != 0, s_ph[p]));
+      }
+    }
   };
   if constexpr (L >= 3 || (L == 2 && MMSE)) {
     // the normal equations built port by port as the coefficients are rebuilt (few live registers)
@@ -284,10 +313,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void p
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       eq::cplx hp[L];
-#pragma unroll
-      for (int v = 0; v < L; ++v) {
-        hp[v] = coef(p, v);
-      }
+      coefs(p, hp);
       eq::mimo_add_port(sys, hp, eq::from_cbf16(grid[static_cast<uint64_t>(p) * plane]));
     }
     float nmax;
@@ -307,10 +333,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void p
 #pragma unroll
     for (int p = 0; p < P; ++p) {
       y[p] = eq::from_cbf16(grid[static_cast<uint64_t>(p) * plane]);
-#pragma unroll
-      for (int v = 0; v < L; ++v) {
-        h[p * L + v] = coef(p, v);
-      }
+      coefs(p, h + p * L);
     }
     equalize_write<P, L, MMSE>(a, lt, gi, j, l, y, h);
   }
