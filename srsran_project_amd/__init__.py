@@ -138,6 +138,15 @@ from .prach import (  # noqa: F401,E402
     prach_geometry,
     prach_physical_root,
 )
+from . import prach_demodulator  # noqa: F401,E402
+from .prach_demodulator import (  # noqa: F401,E402
+    PrachDemodBatch,
+    PrachDemodConfiguration,
+    PrachDemodGeometry,
+    PrachDemodulator,
+    prach_demod_geometry,
+    prach_detector_offsets,
+)
 from . import srs  # noqa: F401,E402
 from .srs import (  # noqa: F401,E402
     SrsBatch,
